@@ -12,6 +12,12 @@ configs[1]: v2, batch 32 mono, 44.1 kHz, n_signal 65536, VAE phase.  Multi-GPU: 
 minibatch is sharded (32 clips per GPU), gradients averaged with bucketed RCCL all-reduce
 overlapped with backward.  Rank 0 prints ONE JSON line.  ``--gpus N`` without a torchrun environment
 re-launches itself under ``torch.distributed.run`` with N ranks (and fails if fewer GPUs are visible).
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the result line.  ``--full`` adds the secondary
+figures that take runs of their own: per-kernel HIP-event timing and roofline, the forward-only leg, the
+forward_only_bf16x6 comparison leg and the CPU baseline.  ``--dump-outputs DIR`` writes what the last timed step
+returned (its logged losses) and the model state it left (float32, a fixed sample of every large tensor) as
+``DIR/<name>.npy``, so that two builds can be compared output for output on the same seeded inputs.
 """
 import argparse
 import json
@@ -280,10 +286,32 @@ def bf16x6_leg(batch: int, n_signal: int):
         return {"forward_only_bf16x6": {"error": repr(e)}}
 
 
+DUMP_BYTES = 56 << 20        # --dump-outputs stays under 64 MB in all (npy headers included)
+DUMP_SAMPLE = 16384           # elements kept of a tensor larger than this (a fixed, seeded sample)
+
+
+def dump_outputs(out_dir: str, logged: dict, model) -> None:
+    """``out_dir/loss.<key>.npy`` for every value the step returned and ``out_dir/state.<key>.npy`` for every floating-point
+    entry of the model's state_dict after it; tensors larger than the per-array budget are replaced by the same seeded sample
+    of their flattened elements in every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    state = {k: v for k, v in model.state_dict().items() if v.is_floating_point()}
+    per = min(DUMP_SAMPLE, DUMP_BYTES // (4 * (len(logged) + len(state))))
+    for k, v in logged.items():
+        np.save(os.path.join(out_dir, f"loss.{k}.npy"), np.asarray(torch.as_tensor(v).detach().float().cpu().numpy()))
+    for k, v in state.items():
+        v = v.detach().float()
+        if v.numel() > per:
+            idx = np.sort(np.random.default_rng(0).choice(v.numel(), per, replace=False))
+            v = v.reshape(-1)[torch.from_numpy(idx).to(v.device)]
+        np.save(os.path.join(out_dir, f"state.{k}.npy"), v.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=32, help="clips per GPU")
     ap.add_argument("--n-signal", type=int, default=65536)
@@ -297,6 +325,12 @@ def main():
     ap.add_argument("--no-graph", action="store_true",
                     help="run the eager step instead of replaying the captured hipGraph (data-parallel runs record the "
                          "bucket all-reduces into the same graph)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary figures after the timed steps: per-kernel timing / roofline and the "
+                         "forward-only leg, the forward_only_bf16x6 leg and the CPU baseline (each can be left out with "
+                         "its --no-* option)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the losses of the last timed step and the model state after it as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--force-graph", action="store_true",
                     help="(no-op since round 6: every config records its step; kept for old command lines)")
@@ -306,6 +340,10 @@ def main():
     ap.add_argument("--forward-leg", default=None, help=argparse.SUPPRESS)   # child process of bf16x6_leg()
     ap.add_argument("--cpu-point", default=None, help=argparse.SUPPRESS)      # child process of cpu_baseline()
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_cpu_baseline = args.no_kernel_timing = args.no_products_leg = True
     if args.cpu_point:
         b, thr, n = (int(v) for v in args.cpu_point.split(","))
         return _cpu_point(b, thr, n)
@@ -438,13 +476,14 @@ def main():
 
     def step(i, eager=False):
         if graphed is not None and not eager:
-            graphed(x, i)
+            logged = graphed(x, i)
         elif use_ddp:
             bufsync.sync()
-            m.training_step(x.detach().clone(), i, capture_safe=use_graph, **sync_kw)
+            logged = m.training_step(x.detach().clone(), i, capture_safe=use_graph, **sync_kw)
         else:
-            m.training_step(x.detach().clone(), i, capture_safe=use_graph)
+            logged = m.training_step(x.detach().clone(), i, capture_safe=use_graph)
         m.on_train_batch_end(None, None, i)       # generator LR schedule (rave/model.py:272-274)
+        return logged
 
     def fence():
         torch.cuda.synchronize()
@@ -459,10 +498,12 @@ def main():
     t0 = time.perf_counter()
     evs[0].record()
     for i in range(args.steps):
-        step(args.warmup + i)
+        logged = step(args.warmup + i)
         evs[i + 1].record()
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, logged, m)
     per_step = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps))
     tt = torch.tensor([dt], dtype=torch.float64, device=dev)
     if use_ddp:

@@ -548,6 +548,96 @@ def golden_v2_wide(name="v2_wide.pt"):
     print(name, os.path.getsize(os.path.join(OUT, name)), "bytes;", len(grads), "gradients; reg", float(reg))
 
 
+def golden_reference_checks(name="reference_checks.pt"):
+    """Outputs of the reference's own classes that tests/test_oracle.py and tests/test_abi_and_host.py compare the oracle
+    and the drop-in modules with: the v2 modules (both paddings), the polyphase / classic PQMF forms, the spectral and
+    Encodec distances and the latent-space wrappers."""
+    from functools import partial
+    from ref_import import import_reference
+    import_reference()
+    from rave import blocks as rb, core, pqmf as rp
+    out = {}
+    # seeded weights (O.seeded_state_dict): the fixture carries the seed, the shapes and the weight_g tensors (a norm
+    # reduction whose last bits may depend on the host).  Inputs are stored whole; outputs above `keep` elements as a fixed
+    # strided sample (_subsample): every `out_step`-th element, every `step`-th of a discriminator feature map
+    seed, step, keep, out_step = 3, 61, 2048, 3
+    out_keep = 4 * keep
+    sub = lambda v: _subsample(v, out_step, out_keep)
+    for causal in (False, True):
+        torch.manual_seed(3)
+        m = build_reference_rave("v2", capacity=10, latent_size=12, causal=causal)
+        m.train()
+        shapes = {k: tuple(v.shape) for k, v in m.state_dict().items()
+                  if k.startswith(("encoder.", "decoder.", "discriminator.")) and k.endswith((".weight_v", ".weight_g", ".weight", ".bias"))}
+        sd = O.seeded_state_dict(shapes, seed)
+        missing = set(m.state_dict()) - set(sd)
+        m.load_state_dict(sd, strict=False)
+        assert all(k.startswith(("pqmf.", "audio_distance.", "multiband_audio_distance.", "latent_", "fidelity", "receptive_field",
+                                 "encoder.warmed_up")) for k in missing), sorted(missing)
+        x = O.synthetic_batch(2, 1, 8192, seed=9)
+        with torch.no_grad():
+            zp, xmb = m.encode(x, return_mb=True)
+            eps = torch.randn(2, 12, zp.shape[-1])
+            z, _ = O.reparametrize(zp, eps)
+            y_mb = m.decoder(z)
+            yr = m.decode(z)
+            feats = m.discriminator(torch.cat([x, yr], 0))
+            dist = m.audio_distance(x, yr)["spectral_distance"]
+        rec = dict(x_mb=sub(xmb), z_params=t(zp), z=t(z), y_mb=sub(y_mb), y_raw=sub(yr),
+                   feature_shapes=[[tuple(f.shape) for f in net] for net in feats],
+                   features=[[_subsample(f, step, keep) for f in net] for net in feats], spectral_distance=t(dist))
+        if not causal:
+            rec.update(x=t(x), seed=seed, shapes=shapes, feature_step=step, feature_keep=keep, out_step=out_step, out_keep=out_keep,
+                       weight_g={k: t(v) for k, v in sd.items() if k.endswith(".weight_g")})
+        out["modules_causal" if causal else "modules"] = rec
+    build_reference_rave("v2", capacity=4, latent_size=4, causal=False)  # reset the causal binding
+
+    b = O.pqmf_buffers(100, 16)
+    x = O.synthetic_batch(2, 1, 4096, seed=1)
+    out["pqmf_forms"] = dict(x=t(x), polyphase=t(rp.reverse_half(rp.polyphase_forward(x, b["hk"]))),
+                             classic=t(rp.reverse_half(rp.classic_forward(x, b["hk"]))))
+    hk = b["hk"]
+    g = torch.Generator().manual_seed(4)
+    x = torch.randn(2, 1, 4096, generator=g)
+    y = torch.randn(2, 16, 256, generator=g)
+    forms = {}
+    for poly in (True, False):
+        m = rp.PQMF(attenuation=100, n_band=16, polyphase=poly)
+        with torch.no_grad():
+            forms["polyphase" if poly else "classic"] = dict(forward=t(m(x)), inverse=t(m.inverse(y)))
+    out["pqmf_noncached"] = dict(x=t(x), y=t(y), **forms)
+
+    g = torch.Generator().manual_seed(2)
+    x = torch.randn(2, 1, 6000, generator=g)
+    y = (x + 0.1 * torch.randn(2, 1, 6000, generator=g))
+    dists = {}
+    for power, normalized, norms in ((1, True, ("L1", "L2")), (2, False, "L2"), (None, True, "L1")):
+        kw = dict(sampling_rate=44100, norm=norms, power=power, normalized=normalized)
+        rec = {}
+        for n_fft in (256, 1024):
+            ya = y.clone().requires_grad_(True)
+            da = core.SpectralDistance(n_fft, **kw)(x, ya)
+            da.backward()
+            rec[n_fft] = dict(distance=t(da), grad_y=sub(ya.grad))
+        ra = core.EncodecAudioDistance([256, 512], partial(core.SpectralDistance, **kw))(x, y)
+        rec["encodec"] = {k: t(v) for k, v in ra.items()}
+        dists[(power, normalized, norms)] = rec
+    out["distances"] = dict(x=t(x), y=t(y), cases=dists, out_step=out_step, out_keep=out_keep)
+
+    enc = lambda n_channels=1: torch.nn.Identity()
+    z = torch.randn(3, 8, 16, generator=torch.Generator().manual_seed(5))
+    w = rb.WasserteinEncoder(enc, noise_augmentation=0)
+    torch.manual_seed(1)
+    zw, rw = w.reparametrize(z)
+    d = rb.DiscreteEncoder(enc, vq_cls=lambda: torch.nn.Identity(), num_quantizers=16, noise_augmentation=4)
+    torch.manual_seed(2)
+    zd, rd = d.reparametrize(z)
+    out["latent"] = dict(z=t(z), wasserstein=(t(zw), t(rw)), spherical=t(rb.SphericalEncoder(enc).reparametrize(z)[0]),
+                         discrete=(t(zd), float(rd)), discrete_state_keys=sorted(d.state_dict()))
+    torch.save(out, os.path.join(OUT, name))
+    print(name, os.path.getsize(os.path.join(OUT, name)), "bytes")
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     golden_pqmf()
@@ -562,3 +652,4 @@ if __name__ == "__main__":
     golden_discrete_step_tiny()
     golden_v2_wide()
     golden_v3_validation_tiny()
+    golden_reference_checks()

@@ -12,19 +12,19 @@ if has probes; then      # (binaries: bash tools/probe/build.sh in the build con
   timeout 60 tools/probe/_var/atomic_fanin > $O/probe_atomic_fanin.txt 2>&1
 fi
 if has bf16; then        # the comparison build (three bf16 pieces, six products: rave_amd/_var/librave_hip_bf16.so) on the same box
-  RAVE_HIP_LIB=$PWD/rave_amd/_var/librave_hip_bf16.so timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-products-leg < /dev/null > $O/bench_n1_bf16x6.log 2>&1
+  RAVE_HIP_LIB=$PWD/rave_amd/_var/librave_hip_bf16.so timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-products-leg < /dev/null > $O/bench_n1_bf16x6.log 2>&1
   RAVE_HIP_LIB=$PWD/rave_amd/_var/librave_hip_bf16.so timeout 200 python tools/bench_layers.py < /dev/null > $O/layers_bf16x6.log 2>&1
 fi
 if has refstep; then     # the unmodified reference training_step on the drop-ins (needs tools/run_reference_step.sh stage)
   [ -d oracle/_ref/reference/rave ] && timeout 600 python tools/run_reference_step.py > $O/reference_step.log 2>&1
 fi
 if has bench; then
-  timeout 400 python bench.py --steps 20 --warmup 5 < /dev/null > $O/bench_n1.log 2>&1
+  timeout 400 python bench.py --full --steps 20 --warmup 5 < /dev/null > $O/bench_n1.log 2>&1
   timeout 200 python bench.py --steps 20 --warmup 5 --no-graph --no-cpu-baseline --no-kernel-timing < /dev/null > $O/bench_n1_eager.log 2>&1
   RAVE_FORCE_DIST=1 timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-kernel-timing < /dev/null > $O/bench_dist1.log 2>&1
 fi
 if has others; then
-  timeout 300 python bench.py --phase gan --steps 8 --warmup 4 --no-cpu-baseline < /dev/null > $O/bench_gan.log 2>&1
+  timeout 300 python bench.py --full --phase gan --steps 8 --warmup 4 --no-cpu-baseline < /dev/null > $O/bench_gan.log 2>&1
   timeout 300 python bench.py --phase gan --skip-dead-grads --steps 8 --warmup 4 --no-cpu-baseline --no-kernel-timing < /dev/null > $O/bench_gan_skip.log 2>&1
   timeout 300 python bench.py --config discrete --phase gan --batch 32 --steps 8 --warmup 4 --no-cpu-baseline < /dev/null > $O/bench_discrete.log 2>&1
   timeout 300 python bench.py --config v3 --phase gan --batch 16 --steps 8 --warmup 4 --no-cpu-baseline < /dev/null > $O/bench_v3.log 2>&1
