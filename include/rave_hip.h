@@ -193,11 +193,12 @@ int rh_residual_unit_fwd_f32(const rh_conv1d_desc* d3, const rh_conv1d_desc* d1,
  * every operand is scaled by a power of two that takes its TENSOR's largest magnitude into [2^14, 2^15) and split into two
  * f16 pieces (csrc/common.hpp).  The scale needs max |x| of each activation operand; it travels in a RANGE SLOT: an array of
  * rh_x6_range_words() uint32 in device memory (32 words in use, one per 128-byte line so that the producers' atomics do not
- * serialise; the rest stays zero), each the bit pattern of a non-negative float -- max |x| is the largest word (any
+ * serialise; the rest stays zero), each the bit pattern of a non-negative float -- max |x| over the FINITE elements (NaN
+ * and +-Inf are left out) is the largest word (any
  * upper bound within a factor of ~2^10 of it keeps f32 accuracy; a too SMALL value overflows f16: the slot must cover the
  * tensor).  rh_x6_set_ranges arms the slots of the NEXT rh_conv1d_fwd_f32 / rh_conv1d_bwd_data_f32 / rh_residual_unit_fwd_f32
  * / rh_conv1d_bwd_weight[_wn]_f32 / rh_conv2d_fwd_f32 / rh_conv2d_bwd_data_f32 / rh_conv2d_bwd_weight_f32 / rh_act_bwd_bias_f32
- * (out = the slot of g) / rh_pqmf_fold_k1_f32 / rh_reparam_fwd_f32 (out = the slot of their output) call of this thread (consumed by that call, like rh_set_kernel_events):
+ * (out = the slot of g) / rh_pqmf_fold_k1_f32 / rh_reparam_fwd_f32 (out = the slot of their output) call of this thread (consumed by that call -- also when it fails validation --, like rh_set_kernel_events):
  *     in_a   weight gradient only: the slot of dy          in_b   the slot of the input activation (x; dy for bwd_data)
  *     out    where the call leaves max |output| (forward: y, bwd_data: dx; atomicMax, the caller zeroes it first) or NULL
  *     out2   rh_residual_unit_fwd_f32: the slot of the intermediate h, or NULL
@@ -473,7 +474,8 @@ int rh_stft_loss_bwd_f32(const float* x, const float* y, const float* window, co
  * weight-gradient kernel of rh_conv1d_fwd_f32 / _bwd_data_f32 / _bwd_weight_f32 / rh_residual_unit_fwd_f32, not its split-K
  * finalize or reduction launches.  The kernel is dispatched with the events as its own start / stop events, so
  * hipEventElapsedTime(start, stop) is the duration rocprofv3 reports for that dispatch.  rh_kernel_events_used() tells whether
- * a launch consumed the pair (and disarms it). */
+ * a launch consumed the pair (and disarms it).  The pair is dropped when the conv / weight-gradient call returns, whether its
+ * main kernel took it or not (a failed call, a kernel without the hook): it never reaches a later call. */
 int rh_set_kernel_events(void* start_event, void* stop_event);
 int rh_kernel_events_used(void);
 int rh_event_create(void** event);                                   /* hipEventCreate (timing enabled) */

@@ -81,9 +81,47 @@ def build(force: bool = False, verbose: bool = False, _variants: bool = True) ->
 
 # Comparison library (never loaded by the product path: rave_amd._lib takes it only through RAVE_HIP_LIB): the x6 kernels in
 # their round 2-5 form -- three bf16 pieces per operand, six partial products, no scales / range slots (common.hpp:
-# RH_X6_F16 = 0) -- for bench.py's `forward_only_bf16x6` leg and A/B runs.  Only the sources that see the macro are recompiled.
-VARIANT_SOURCES = [s for s in SOURCES if s.startswith("conv_x6_i")] + [
-    "conv_x6.hip", "unit_x6.hip", "conv_host.hip", "conv_wgrad_x6.hip", "conv_wgrad.hip", "conv2d_x6.hip", "api.cpp"]
+# RH_X6_F16 = 0) -- for bench.py's `forward_only_bf16x6` leg and A/B runs.  Only the sources that see the piece layout are
+# recompiled: every translation unit whose CODE (comments and string literals do not count) names one of PIECE_TOKENS or
+# includes one of PIECE_HEADERS.  Derived from the sources, so that a new user of the layout cannot be left out and link its
+# f16-layout object next to bf16-layout ones.
+PIECE_TOKENS = ("RH_X6_F16", "kX6P", "RH_X6_NPIECE", "rh_x6_frag")
+PIECE_HEADERS = ("conv_x6_kernel.inc", "conv2d_x6.hpp")
+
+
+def strip_comments(text: str) -> str:
+    """C / C++ source without its comments and with its string / character literals emptied (line structure kept)."""
+    import re
+    pat = re.compile(r'//[^\n]*|/\*.*?\*/|"(?:\\.|[^"\\\n])*"|\'(?:\\.|[^\'\\\n])*\'', re.S)
+
+    def blank(m):
+        t = m.group(0)
+        if t[0] in "\"'":
+            return t[0] * 2
+        return "\n" * t.count("\n") or " "
+    return pat.sub(blank, text)
+
+
+def uses_piece_layout(text: str) -> bool:
+    """True iff the translation unit's code names one of PIECE_TOKENS or includes one of PIECE_HEADERS."""
+    import re
+    code = strip_comments(text)
+    if any(re.search(r"\b%s\b" % re.escape(t), code) for t in PIECE_TOKENS):
+        return True
+    includes = re.findall(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', re.sub(r"/\*.*?\*/", " ", text, flags=re.S), re.M)
+    return any(os.path.basename(i) in PIECE_HEADERS for i in includes)
+
+
+def _variant_sources():
+    out = []
+    for s in SOURCES:
+        with open(os.path.join(CSRC, s)) as f:
+            if uses_piece_layout(f.read()):
+                out.append(s)
+    return out
+
+
+VARIANT_SOURCES = _variant_sources()
 VAR = os.path.join(HERE, "_var")
 
 

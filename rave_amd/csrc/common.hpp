@@ -16,6 +16,11 @@ int rh_check_launch(const char* what);
 // events as its own start / stop events (hipExtLaunchKernelGGL: the dispatch's own timestamps, what rocprofv3 reports).
 extern thread_local hipEvent_t rh_ev_start, rh_ev_stop;
 extern thread_local int rh_ev_used;
+// Declared first in every conv / weight-gradient entry point: the events are disarmed when the call returns, on every path --
+// a call that failed validation, or launched a kernel without the hook, must not hand them to the next call of the thread.
+struct RhKernelEventsScope {
+    ~RhKernelEventsScope() { rh_ev_start = rh_ev_stop = nullptr; }
+};
 #ifdef __HIP__
 template <typename K, typename... A>
 inline void rh_launch_main(K kern, dim3 grid, dim3 block, size_t lds, hipStream_t stream, A... args) {
@@ -97,7 +102,7 @@ typedef __bf16 rh_x6_frag __attribute__((ext_vector_type(8)));
 constexpr int kX6P = RH_X6_NPIECE;             // pieces (16-byte fragments) stored per octet of 8 K values
 
 // A range slot: kRangeWords words, ONE PER 128-BYTE LINE (kRangeStride words apart), each the bit pattern of a non-negative
-// float; the tensor's max |x| is the largest of them.  Producers atomicMax their workgroups' maxima into word
+// float; the tensor's max |x| over its FINITE elements (rh_absmax) is the largest of them.  Producers atomicMax their workgroups' maxima into word
 // (workgroup id) % kRangeWords.  Agent-scope atomics are performed memory-side on this chip and serialise per LINE: 1024
 // workgroups publishing into 32 words of one line cost +5.4 us per launch, into 32 lines +0.4 us (tools/probe/atomic_fanin.hip,
 // profiles/round6_probe_atomic_fanin.txt).  Must be zero before the producer runs.
@@ -105,8 +110,9 @@ constexpr int kRangeWords = 32;
 constexpr int kRangeStride = 32;
 constexpr int kRangeSlotWords = kRangeWords * kRangeStride;      // uint32 per slot (4 KB)
 // Power-of-two scale that takes a tensor with max |x| = float(bits) into [2^14, 2^15), as a float bit pattern; *inv_exp = the
-// biased exponent of its inverse.  Exponents are clamped to normal floats: tensors whose maximum is below 2^-111 lose
-// precision (their products underflow f32 anyway), Inf / NaN maxima scale like the largest finite float.
+// biased exponent of its inverse.  Exponents are clamped to normal floats: a tensor whose maximum is below 2^-111 is scaled by
+// 2^125 only (its elements are then held to max(2^-24 |x|, 2^-150): exact for f32 subnormals), Inf / NaN maxima scale like
+// the largest finite float.
 __host__ __device__ __forceinline__ unsigned rh_x6_scale_bits(unsigned amax_bits, int* inv_exp) {
     int e = (int)((amax_bits >> 23) & 0xffu);
     if (e > 254) e = 254;
@@ -116,12 +122,14 @@ __host__ __device__ __forceinline__ unsigned rh_x6_scale_bits(unsigned amax_bits
     *inv_exp = 254 - se;
     return (unsigned)se << 23;
 }
-// scale of the product: 1 / (scale_a * scale_b) as a float, exponent clamped to the normal range
+// scale of the product: 1 / (scale_a * scale_b) as a float.  Below the normal range it is the SUBNORMAL power of two (exact:
+// one mantissa bit; products of quiet tensors -- max |x| * max |w| below ~2^-97 -- are normal floats that a clamp to 2^-126
+// would return up to 2^23 times too large), 0 below 2^-149; above, clamped to the largest normal exponent.
+// Branch-free (selects only): a branch here splits the prologue of every x6 kernel and costs ~2 % of a training step.
 __host__ __device__ __forceinline__ unsigned rh_x6_unscale_bits(int inv_exp_a, int inv_exp_b) {
-    int e = inv_exp_a + inv_exp_b - 127;
-    if (e < 1) e = 1;
-    if (e > 254) e = 254;
-    return (unsigned)e << 23;
+    const int e = min(inv_exp_a + inv_exp_b - 127, 254);
+    const unsigned sub = e >= -22 ? 1u << ((22 + e) & 31) : 0u;
+    return e >= 1 ? (unsigned)e << 23 : sub;
 }
 #ifdef __HIP__
 __device__ __forceinline__ unsigned rh_range_max(const unsigned* slot) {       // uniform (scalar loads)
@@ -145,9 +153,14 @@ __device__ __forceinline__ void rh_range_publish(unsigned* slot, float amax_lane
         atomicMax(slot + (salt % kRangeWords) * kRangeStride, __float_as_uint(m));
     }
 }
-__device__ __forceinline__ float rh_absmax(float m, float v) {                 // max(m, |v|) as one v_max_f32
+// max(m, |v|) over FINITE v: the fold of every range slot (publishers, rh_amax_f32).  NaN and +-Inf are left out -- an Inf maximum
+// would scale the tensor like the largest finite float and flush every finite element below the f16 pieces; left out, an Inf
+// element converts to Inf / NaN pieces and turns exactly the outputs it reaches non-finite.  (v_cmp_class + v_cndmask +
+// v_max_f32; m is a finite non-negative running maximum.)
+__device__ __forceinline__ float rh_absmax(float m, float v) {
+    const float f = __builtin_isfinite(v) ? v : 0.f;
     float r;
-    asm("v_max_f32 %0, %1, |%2|" : "=v"(r) : "v"(m), "v"(v));
+    asm("v_max_f32 %0, %1, |%2|" : "=v"(r) : "v"(m), "v"(f));
     return r;
 }
 #if RH_X6_F16

@@ -1249,6 +1249,7 @@ extern "C" int rh_conv2d_pack_f32(const rh_conv2d_desc* d, const float* w, float
 
 extern "C" int rh_conv2d_fwd_f32(const rh_conv2d_desc* d, const float* x, const float* wp_fwd, const float* bias,
                                  float* y, rh_stream_t stream) {
+    const RhKernelEventsScope events;
     const unsigned* in_range = nullptr;
     unsigned* out_range = nullptr;
     rh_take_ranges(nullptr, &in_range, &out_range, nullptr);       // consumed by this call whatever happens below
@@ -1293,6 +1294,7 @@ extern "C" int rh_conv2d_fwd_f32(const rh_conv2d_desc* d, const float* x, const 
 
 extern "C" int rh_conv2d_bwd_data_f32(const rh_conv2d_desc* d, const float* dy, const float* y, const float* wp_bwd,
                                       float* dx, rh_stream_t stream) {
+    const RhKernelEventsScope events;
     const unsigned* in_range = nullptr;
     unsigned* out_range = nullptr;
     rh_take_ranges(nullptr, &in_range, &out_range, nullptr);
@@ -1363,6 +1365,7 @@ extern "C" int64_t rh_conv2d_workspace_bytes(const rh_conv2d_desc* d) {
 extern "C" int rh_conv2d_bwd_weight_f32(const rh_conv2d_desc* d, const float* dy, const float* y, const float* x,
                                         float* dw, float* dbias, void* workspace, int64_t workspace_bytes,
                                         rh_stream_t stream_) {
+    const RhKernelEventsScope events;
     const unsigned *dy_range = nullptr, *x_range = nullptr;
     rh_take_ranges(&dy_range, &x_range, nullptr, nullptr);
     if (int e = validate2(d)) return e;

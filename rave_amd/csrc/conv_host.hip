@@ -816,6 +816,7 @@ extern "C" int rh_conv1d_plan_info(const rh_conv1d_desc* d, int which, int has_b
 extern "C" int rh_conv1d_fwd_f32(const rh_conv1d_desc* d, const float* x, const float* wp_fwd,
                                  const float* bias, const float* snake_alpha, const float* residual,
                                  float* y, void* workspace, int64_t workspace_bytes, rh_stream_t stream) {
+    const RhKernelEventsScope events;
     ConvP p{};
     rh_take_ranges(nullptr, &p.in_range, &p.out_range, nullptr);       // consumed by this call whatever happens below
     const unsigned* const in_range = p.in_range;
@@ -839,6 +840,7 @@ extern "C" int rh_conv1d_bwd_data_f32(const rh_conv1d_desc* d, const float* dy, 
                                       const float* x, const float* snake_alpha, const float* add,
                                       float* dx, void* workspace, int64_t workspace_bytes,
                                       rh_stream_t stream) {
+    const RhKernelEventsScope events;
     ConvP p{};
     rh_take_ranges(nullptr, &p.in_range, &p.out_range, nullptr);
     const unsigned* const in_range = p.in_range;
@@ -874,19 +876,23 @@ extern "C" int64_t rh_conv1d_workspace_bytes(const rh_conv1d_desc* d) {
 extern "C" int rh_conv1d_bwd_weight_f32(const rh_conv1d_desc* d, const float* dy, const float* x,
                                         const float* snake_alpha, float* dw, float* dbias,
                                         void* workspace, int64_t workspace_bytes, rh_stream_t stream) {
+    const RhKernelEventsScope events;
+    const RhWgradArmed armed = rh_wgrad_take_armed(true);          // consumed by this call whatever happens below
     if (int e = validate(d)) return e;
     RH_REQUIRE(dw && (d->batch == 0 || (dy && x)), RH_ERR_INVALID, "conv1d_bwd_weight: null pointer");
     RH_REQUIRE(d->act != RH_ACT_SNAKE || snake_alpha, RH_ERR_INVALID, "conv1d_bwd_weight: snake needs alpha");
-    return rh_wgrad_run(d, dy, x, snake_alpha, dw, dbias, workspace, workspace_bytes, (hipStream_t)stream);
+    return rh_wgrad_run(d, dy, x, snake_alpha, dw, dbias, workspace, workspace_bytes, (hipStream_t)stream, armed);
 }
 
 extern "C" int rh_conv1d_bwd_weight_wn_f32(const rh_conv1d_desc* d, const float* dy, const float* x, const float* snake_alpha,
                                            const float* v, const float* g, const float* norms, float* dw_scratch, float* dv,
                                            float* dg, float* dbias, void* workspace, int64_t workspace_bytes, rh_stream_t stream) {
+    const RhKernelEventsScope events;
+    const RhWgradArmed armed = rh_wgrad_take_armed(false);         // consumed by this call whatever happens below
     if (int e = validate(d)) return e;
     RH_REQUIRE(dw_scratch && v && g && norms && dv && dg && (d->batch == 0 || (dy && x)), RH_ERR_INVALID,
                "conv1d_bwd_weight_wn: null pointer");
     RH_REQUIRE(d->act != RH_ACT_SNAKE || snake_alpha, RH_ERR_INVALID, "conv1d_bwd_weight_wn: snake needs alpha");
     const RhWnTail tail{v, g, norms, dv, dg};
-    return rh_wgrad_run(d, dy, x, snake_alpha, dw_scratch, dbias, workspace, workspace_bytes, (hipStream_t)stream, &tail);
+    return rh_wgrad_run(d, dy, x, snake_alpha, dw_scratch, dbias, workspace, workspace_bytes, (hipStream_t)stream, armed, &tail);
 }

@@ -341,7 +341,7 @@ __global__ __launch_bounds__(256) void splitk_finalize_kernel(const ConvP p, lon
         if (p.add) v += p.add[idx];
         if (p.out_act == RH_ACT_LEAKY) v = v > 0.f ? v : v * p.out_slope;
         p.out[idx] = v;
-        mx = fmaxf(mx, fabsf(v));
+        mx = rh_absmax(mx, v);
     }
     if (p.out_range) {
         __shared__ float red[4];
@@ -386,7 +386,7 @@ __global__ __launch_bounds__(256) void splitk_finalize4_kernel(const ConvP p, lo
             for (int i = 0; i < 4; ++i) v[i] = v[i] > 0.f ? v[i] : v[i] * p.out_slope;
         }
         *reinterpret_cast<f32x4*>(p.out + idx) = v;
-        mx = fmaxf(mx, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
+        mx = rh_absmax(rh_absmax(mx, v[0]), v[1]); mx = rh_absmax(rh_absmax(mx, v[2]), v[3]);
     }
     if (p.out_range) {
         __shared__ float red[4];

@@ -147,8 +147,17 @@ struct RhWnTail {
     float* dv;
     float* dg;
 };
+// what rh_x6_set_ranges / rh_defer_reduce armed for the next weight-gradient call of this thread: taken (and disarmed) by
+// rh_wgrad_take_armed as the FIRST statement of every weight-gradient entry point, so that a call that fails validation
+// cannot leave it to the next, unrelated call
+struct RhWgradArmed {
+    rh_reduce_item* defer;          // null unless the caller armed rh_defer_reduce (the weight-norm tail never defers)
+    const unsigned* dy_range;
+    const unsigned* x_range;
+};
+RhWgradArmed rh_wgrad_take_armed(bool may_defer);
 int rh_wgrad_run(const rh_conv1d_desc* d, const float* dy, const float* x, const float* alpha, float* dw, float* dbias, void* ws,
-                 int64_t ws_bytes, hipStream_t stream, const RhWnTail* tail = nullptr);
+                 int64_t ws_bytes, hipStream_t stream, const RhWgradArmed& armed, const RhWnTail* tail = nullptr);
 
 int rh_conv_fill_fwd(const rh_conv1d_desc* d, ConvP* p);
 int rh_conv_fill_dgrad(const rh_conv1d_desc* d, ConvP* p);

@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256) void smallc_fwd_kernel(const SmallP p) {
             for (int i = 0; i < KC; ++i) acc = fmaf(wl[m * PITCH + i], xv[i], acc);
             if (leaky) acc = acc > 0.f ? acc : acc * p.out_slope;
             dst[(long)m * p.l_out] = acc;
-            amax = fmaxf(amax, fabsf(acc));
+            amax = rh_absmax(amax, acc);
         }
     }
     if (p.out_range) {           // (uniform; every thread of the workgroup gets here)

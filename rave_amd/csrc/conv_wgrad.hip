@@ -312,7 +312,7 @@ __global__ __launch_bounds__(256) void bias_grad2d_kernel(const float* __restric
                 float v = dy[base + e];
                 if (y) v *= rh_act_grad(y[base + e], act, slope, 0.f);
                 if (g_out) g_out[base + e] = v;
-                mx = fmaxf(mx, fabsf(v));
+                mx = rh_absmax(mx, v);
                 s += v;
             }
         }
@@ -803,14 +803,21 @@ extern "C" int rh_reduce_partials_batched_f32(const rh_reduce_item* items, int32
     return RH_OK;
 }
 
-int rh_wgrad_run(const rh_conv1d_desc* d, const float* dy, const float* x, const float* alpha,
-                 float* dw, float* dbias, void* ws, int64_t ws_bytes, hipStream_t stream, const RhWnTail* tail) {
-    rh_reduce_item* const defer = tail ? nullptr : g_defer_item;       // (consumed by this call whatever happens below)
+RhWgradArmed rh_wgrad_take_armed(bool may_defer) {
+    RhWgradArmed a{may_defer ? g_defer_item : nullptr, nullptr, nullptr};
     g_defer_item = nullptr;
+    rh_take_ranges(&a.dy_range, &a.x_range, nullptr, nullptr);
+    return a;
+}
+
+int rh_wgrad_run(const rh_conv1d_desc* d, const float* dy, const float* x, const float* alpha,
+                 float* dw, float* dbias, void* ws, int64_t ws_bytes, hipStream_t stream, const RhWgradArmed& armed,
+                 const RhWnTail* tail) {
+    rh_reduce_item* const defer = tail ? nullptr : armed.defer;
     WgradP p{};
     fill(d, &p);
-    const unsigned *dy_range = nullptr, *x_range = nullptr;
-    rh_take_ranges(&dy_range, &x_range, nullptr, nullptr);
+    const unsigned* const dy_range = armed.dy_range;
+    const unsigned* const x_range = armed.x_range;
     const bool have_ranges = !RH_X6_F16 || (dy_range && x_range);
     auto through_dw = [&](int e) {
         if (e || !tail) return e;

@@ -717,7 +717,7 @@ __global__ __launch_bounds__(256) void reparam_fwd_kernel(const float* __restric
         const float var = __fmul_rn(sd, sd);
         const float zv = __fadd_rn(__fmul_rn(eps[e], sd), mean);
         zs[e] = zv;
-        amax = fmaxf(amax, fabsf(zv));
+        amax = rh_absmax(amax, zv);
         s += __fsub_rn(__fsub_rn(__fadd_rn(__fmul_rn(mean, mean), var), logf(var)), 1.f);
     }
     const float t = block_sum(s, red);
@@ -852,9 +852,9 @@ __global__ __launch_bounds__(256) void amax_kernel(const float* __restrict__ x, 
     const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         const f32x4 v = x4[i];
-        m = fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+        m = rh_absmax(rh_absmax(m, v[0]), v[1]); m = rh_absmax(rh_absmax(m, v[2]), v[3]);
     }
-    for (long i = 4 * n4 + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) m = fmaxf(m, fabsf(x[i]));
+    for (long i = 4 * n4 + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) m = rh_absmax(m, x[i]);
     __shared__ float red[4];
     rh_range_publish(slot, m, blockIdx.x, red);
 }

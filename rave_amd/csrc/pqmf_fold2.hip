@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void pqmf_fold_k1v2_kernel(const float* __rest
         *reinterpret_cast<f32x4*>(ob + l16 * kOP + 32 * wave + 16 * nb + 4 * lg) = o;
 #pragma unroll
         for (int r4 = 0; r4 < 4; ++r4)
-            if (n0 + 32 * wave + 16 * nb + 4 * lg + r4 < n_frames) amax = fmaxf(amax, fabsf(o[r4]));
+            if (n0 + 32 * wave + 16 * nb + 4 * lg + r4 < n_frames) amax = rh_absmax(amax, o[r4]);
     }
     __syncthreads();
     // ---- whole band rows out: 16 bands x 128 frames, 16 bytes per lane

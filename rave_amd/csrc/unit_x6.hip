@@ -77,8 +77,9 @@ __global__ __launch_bounds__(256, 2) void unit_x6_kernel(const UnitP u) {
     const unsigned hsc_bits = rh_x6_scale_bits(__float_as_uint(hbound), &inv_h);
     (void)rh_x6_scale_bits(u.w1_range[0], &inv_w1);
     const float osc2 = __uint_as_float(rh_x6_unscale_bits(inv_w1, inv_h));                   // accumulators of GEMM 2 -> conv1(h)
-    // accumulators of GEMM 1 -> scaled h in ONE multiplication: osc1 * hsc, exponents added and clamped
-    const float h2sc = __uint_as_float(rh_x6_unscale_bits((int)(__float_as_uint(osc1) >> 23), (int)(hsc_bits >> 23)));
+    // accumulators of GEMM 1 -> scaled h in ONE multiplication: osc1 * hsc, exponents added (from the inverses' exponents, not
+    // from osc1's bits: osc1 may be subnormal) and clamped
+    const float h2sc = __uint_as_float(rh_x6_unscale_bits(inv_w3 + (int)(hsc_bits >> 23) - 127, inv_x));
 #else
     const float xsc = 1.f, osc1 = 1.f, osc2 = 1.f, h2sc = 1.f;
 #endif
@@ -392,14 +393,15 @@ extern "C" int rh_residual_unit_fused(const rh_conv1d_desc* d3, const rh_conv1d_
 // intermediate for the backward pass, or NULL (inference).  Replaces Residual(DilatedUnit(...)) (rave/blocks.py:31-45,83-112).
 extern "C" int rh_residual_unit_fwd_f32(const rh_conv1d_desc* d3, const rh_conv1d_desc* d1, const float* x, const float* wp3_fwd,
                                         const float* wp1_fwd, float* h, float* y, rh_stream_t stream) {
+    const RhKernelEventsScope events;
+    const unsigned* x_range = nullptr;
+    unsigned *y_range = nullptr, *h_range = nullptr;
+    rh_take_ranges(nullptr, &x_range, &y_range, &h_range);       // consumed by this call whatever happens below
     RH_REQUIRE(unit_enabled() && unit_shape_ok(d3, d1), RH_ERR_UNSUPPORTED, "residual_unit_fwd: geometry not fusable");
     RH_REQUIRE(x && wp3_fwd && wp1_fwd && y, RH_ERR_INVALID, "residual_unit_fwd: null pointer");
     UnitP u{};
     size_t lds = 0;
     dim3 grid;
-    const unsigned* x_range = nullptr;
-    unsigned *y_range = nullptr, *h_range = nullptr;
-    rh_take_ranges(nullptr, &x_range, &y_range, &h_range);
     RH_REQUIRE(!RH_X6_F16 || x_range, RH_ERR_INVALID, "residual_unit_fwd: the f16 kernels need the input's range slot (rh_x6_set_ranges)");
     u.c.in_range = x_range;
     if (int e = fill_unit(d3, d1, &u, &lds, &grid)) {

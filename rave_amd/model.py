@@ -490,6 +490,7 @@ class GraphedTrainingStep:
             self.eps = torch.zeros(self.x.shape[0], model.latent_size, self.x.shape[-1] // self._hop(), device=self.x.device)
         self.warmup_iters = warmup_iters
         self.graphs = {}
+        self.range_pools = {}            # key -> the range-slot pools the recording took (ops.range_capture_end): alive with the graph
         self.logged = {}
 
     def _hop(self) -> int:
@@ -601,8 +602,11 @@ class GraphedTrainingStep:
                         _ops.abandon_side_streams(rejoin=True)
             except Exception as e:                # noqa: BLE001 -- the recording could not be closed either
                 err = err or e
+            from . import ops as _ops
+            # the slot pools taken inside the recording belong to the graph (each replay re-zeroes them): eager work from here on
+            # takes its slots from a fresh pool
+            pools = _ops.range_capture_end()
             if err is not None:
-                from . import ops as _ops
                 _ops.abandon_side_streams()
                 for _ in range(3):
                     try:
@@ -614,6 +618,7 @@ class GraphedTrainingStep:
                 raise err
             # the capture itself does not execute anything: parameters are still the restored ones
             self.graphs[key] = (g, logged)
+            self.range_pools[key] = pools
         g, logged = self.graphs[key]
         if not _replay:
             return logged

@@ -250,11 +250,14 @@ def _ws(nbytes: int, device) -> Optional[Tensor]:
 # counter.  A tensor without a (current) slot -- produced by a torch op, a view, modified in place -- gets one from a pass of
 # rh_amax_f32 the first time a convolution consumes it.  Slots come from a zeroed pool; RAVE.training_step takes a fresh pool per
 # step (range_reset: one fill launch -- recorded into a hipGraph it re-zeroes the slots at every replay, so a replayed step
-# computes the same scales as an eager one).
+# computes the same scales as an eager one).  A pool taken inside a capture belongs to the graph (every replay re-zeroes it): eager
+# work after the capture never takes a slot from it (_new_range starts a fresh pool; GraphedTrainingStep also drops it from the
+# table when the recording ends and keeps it alive with the graph, range_capture_end).
 _RANGES = L.lib.rh_x6_uses_ranges() == 1
 _RANGE_WORDS = L.lib.rh_x6_range_words()
 _RANGE_SLOTS = 2048     # 4 KB each: more than any step of the shipped configs uses (a pool that runs out mid-step is replaced)
-_RANGE_POOLS = {}        # device -> [pool, cursor, previous pool (kept alive: a side stream may still read it), stream of the reset]
+_RANGE_POOLS = {}        # device -> [pool, cursor, previous pool (kept alive: a side stream may still read it), stream of the reset,
+#                                     taken inside a stream capture]
 
 
 def range_reset(device=None, _exhausted: bool = False) -> None:
@@ -278,7 +281,20 @@ def range_reset(device=None, _exhausted: bool = False) -> None:
             main = st[3] if st else cur
         else:
             main = cur
-        _RANGE_POOLS[dev] = [pool, 0, prev, main]
+        _RANGE_POOLS[dev] = [pool, 0, prev, main, torch.cuda.is_current_stream_capturing()]
+
+
+def range_capture_end(device=None) -> list:
+    """Call when a stream capture has ended (successfully or not): the pools taken inside it are dropped from the table, so that
+    no later eager launch takes a slot that the graph's replays re-zero (or, before the first replay, that was never zeroed).
+    Returns them: the caller keeps them alive as long as the graph exists."""
+    out = []
+    for dev in ([device] if device is not None else list(_RANGE_POOLS)):
+        st = _RANGE_POOLS.get(dev)
+        if st is not None and st[4]:
+            out += [t for t in (st[0], st[2]) if t is not None]
+            del _RANGE_POOLS[dev]
+    return out
 
 
 def _ranges_on() -> bool:
@@ -287,6 +303,9 @@ def _ranges_on() -> bool:
 
 def _new_range(device) -> Tensor:
     st = _RANGE_POOLS.get(device)
+    if st is not None and st[4] and not torch.cuda.is_current_stream_capturing():
+        range_reset(device)           # the pool of a finished capture (range_capture_end was not called): never handed out eagerly
+        st = _RANGE_POOLS[device]
     if st is None or st[1] >= _RANGE_SLOTS:
         range_reset(device, _exhausted=st is not None)
         st = _RANGE_POOLS[device]
@@ -298,6 +317,24 @@ def _new_range(device) -> Tensor:
 def _attach_range(t: Optional[Tensor], slot: Optional[Tensor]) -> None:
     if t is not None and slot is not None:
         t._rh_range = (slot, t._version)
+
+
+def _disarm() -> None:
+    """Drop whatever rh_x6_set_ranges / rh_defer_reduce armed for the next call of this thread."""
+    L.lib.rh_x6_set_ranges(None, None, None, None)
+    L.lib.rh_defer_reduce(None)
+
+
+def _armed_call(fn):
+    """Decorator of the functions that arm the thread-local state of the library and then make the C call that consumes it:
+    if anything raises in between, the state is dropped (it would otherwise reach the next, unrelated call of the thread)."""
+    def wrapped(*a, **k):
+        try:
+            return fn(*a, **k)
+        except BaseException:
+            _disarm()
+            raise
+    return wrapped
 
 
 _RANGE_MISS = None       # diagnostics (range_miss_log_begin): [(tag, shape)] of the tensors that needed an rh_amax_f32 pass
@@ -314,30 +351,61 @@ def range_miss_log_end():
     return out
 
 
-def _valid_slot(t: Tensor):
+def _stream_of(handle, device) -> torch.cuda.Stream:
+    cur = torch.cuda.current_stream(device)
+    if cur.cuda_stream == handle:
+        return cur
+    for st in _SIDE.values():
+        if st.cuda_stream == handle:
+            return st
+    return torch.cuda.ExternalStream(handle, device=device)
+
+
+def _valid_slot(t: Tensor, s):
+    """The slot attached to ``t`` if it is current, for a consumer on stream ``s``.  A slot that rh_amax_f32 filled on ANOTHER
+    stream (the weight-gradient side stream, _arm_wgrad_ranges under _OnSide) carries the event recorded right behind that pass:
+    a consumer on a different stream waits for it (for the pass only, not for the weight-gradient kernels queued after it).
+    Such a slot filled inside a stream capture is not used outside it (and vice versa: an eager one inside a capture needs no
+    wait -- the pass was queued before the recording)."""
     r = getattr(t, "_rh_range", None)
-    if r is not None and r[1] == t._version and r[0].device == t.device:
-        return r[0]
-    return None
+    if r is None or r[1] != t._version or r[0].device != t.device:
+        return None
+    if len(r) > 2 and r[2][0] != s:
+        _, captured, ev = r[2]
+        now = torch.cuda.is_current_stream_capturing()
+        if captured and not now:
+            return None
+        if captured == now:
+            _stream_of(s, t.device).wait_event(ev)
+    return r[0]
 
 
 def _range_of(t: Tensor, s, tag: str = "") -> Tensor:
     """The range slot of ``t``: the one its producer left -- also through a view that covers the whole producer tensor (same
-    elements, same maximum; views share the version counter) --, else computed now (one pass over ``t`` on stream ``s``)."""
-    slot = _valid_slot(t)
+    elements, same maximum; views share the version counter) --, else computed now (one pass over ``t`` on stream ``s``).
+    The contract rests on the version counter: a write that bypasses it -- through ``.data``, or raw (ctypes / C ABI) writes
+    into an existing tensor -- leaves a stale slot behind and is outside it (a bigger stale maximum costs accuracy, a smaller
+    one overflows the f16 pieces)."""
+    slot = _valid_slot(t, s)
     if slot is not None:
         return slot
     base = t._base
     if base is not None and base.numel() == t.numel():
-        slot = _valid_slot(base)
+        slot = _valid_slot(base, s)
         if slot is not None:
-            t._rh_range = (slot, t._version)
+            t._rh_range = (slot, t._version) + tuple(base._rh_range[2:])
             return slot
     if _RANGE_MISS is not None:
         _RANGE_MISS.append((tag, tuple(t.shape)))
     slot = _new_range(t.device)
     L.check(L.lib.rh_amax_f32(L.ptr(t), t.numel(), L.ptr(slot), s), "amax")
     _attach_range(t, slot)
+    side = next((st for st in _SIDE.values() if st.cuda_stream == s), None)
+    if side is not None:
+        # filled on the side stream: a consumer on the compute stream must not read it before this pass has run (_valid_slot)
+        ev = torch.cuda.Event()
+        ev.record(side)
+        t._rh_range = (slot, t._version, (s, torch.cuda.is_current_stream_capturing(), ev))
     return slot
 
 
@@ -351,6 +419,7 @@ def _fwd(d, x, wp, bias, alpha, residual, y, s):
             rin = _range_of(x, s, "fwd x")
         rout = _new_range(y.device)
 
+    @_armed_call
     def run(out, ranges=True):
         if ranges and rout is not None:
             L.lib.rh_x6_set_ranges(None, L.ptr(rin), L.ptr(rout), None)
@@ -371,6 +440,7 @@ def _unit_fwd(d3, d1, x, wp3, wp1, h, y, s):
         rin, ry = _range_of(x, s, "unit x"), _new_range(x.device)
         rh = _new_range(x.device) if h is not None else None
 
+    @_armed_call
     def run(o_y, o_h):
         if rin is not None:
             L.lib.rh_x6_set_ranges(None, L.ptr(rin), L.ptr(ry), L.ptr(rh))
@@ -414,6 +484,7 @@ def _dgrad(d, dy, wp, x, alpha, add, dx, s):
             rin = _range_of(dy, s, "dgrad dy")
         rout = _new_range(dx.device)
 
+    @_armed_call
     def run(out, ranges=True):
         if ranges and rout is not None:
             L.lib.rh_x6_set_ranges(None, L.ptr(rin), L.ptr(rout), None)
@@ -668,6 +739,7 @@ def _arm_wgrad_ranges(dy, x, s, d=None) -> None:
 
 def _wgrad(d, dy, x, alpha, dw, db, ws, nbytes, s, defer=None):
     """``defer``: a ReduceItem -- the call may leave the reduction of its K-slice partials to the caller (rh_defer_reduce)."""
+    @_armed_call
     def run(o_dw, o_db):
         _arm_wgrad_ranges(dy, x, s, d)
         if defer is not None:
@@ -797,10 +869,14 @@ def _wgrad_wn(d, dy, x, alpha, dw, db, v, g, norms, ws, nbytes, s, slot_v=None, 
         if len(_WN_PENDING) >= _WN_BATCH_MAX:      # (we are on the side stream here: the batch runs beside the data-gradient chain)
             _flush_wn_pending(s)
         return dv, dg
-    _arm_wgrad_ranges(dy, x, s, d)
-    L.check(L.lib.rh_conv1d_bwd_weight_wn_f32(C.byref(d), L.ptr(dy), L.ptr(x), L.ptr(alpha), L.ptr(v), L.ptr(g), L.ptr(norms),
-                                              L.ptr(dw), L.ptr(dv), L.ptr(dg), L.ptr(db), L.ptr(ws), nbytes, s),
-            "conv1d_bwd_weight_wn")
+
+    @_armed_call
+    def run():
+        _arm_wgrad_ranges(dy, x, s, d)
+        return L.lib.rh_conv1d_bwd_weight_wn_f32(C.byref(d), L.ptr(dy), L.ptr(x), L.ptr(alpha), L.ptr(v), L.ptr(g), L.ptr(norms),
+                                                 L.ptr(dw), L.ptr(dv), L.ptr(dg), L.ptr(db), L.ptr(ws), nbytes, s)
+
+    L.check(run(), "conv1d_bwd_weight_wn")
     return dv, dg
 
 
@@ -1082,6 +1158,7 @@ class _Conv2dFn(torch.autograd.Function):
         y = torch.empty(b, c_out, h_out, w_out, device=dev, dtype=torch.float32)
         rin, rout = _conv2d_ranges(d, 0, x, dev, s, "conv2d x")
 
+        @_armed_call
         def run_fwd():
             if rout is not None:
                 L.lib.rh_x6_set_ranges(None, L.ptr(rin), L.ptr(rout), None)
@@ -1128,6 +1205,7 @@ class _Conv2dFn(torch.autograd.Function):
             dx = torch.empty_like(x)
             rin, rout = _conv2d_ranges(d, 1, dy, dy.device, s, "conv2d dy") if y is None else (None, None)
 
+            @_armed_call
             def run_dgrad():
                 if rout is not None:
                     L.lib.rh_x6_set_ranges(None, L.ptr(rin), L.ptr(rout), None)
@@ -1146,6 +1224,7 @@ class _Conv2dFn(torch.autograd.Function):
             rdy = _range_of(dy, s, "conv2d wgrad dy") if use_r else None
             rx = _range_of(x, s, "conv2d wgrad x") if use_r else None
 
+            @_armed_call
             def run_wgrad():
                 if use_r:
                     L.lib.rh_x6_set_ranges(L.ptr(rdy), L.ptr(rx), None, None)

@@ -506,3 +506,33 @@ def test_product_pqmf_filter_bank_is_bit_identical_to_the_reference_buffers():
     assert torch.equal(m.h, g["h"]) and torch.equal(m.hk, g["hk"])
     assert torch.equal(m.forward_conv.weight.detach(), g["w_fwd"])
     assert torch.equal(m.inverse_conv.weight.detach(), g["w_inv"])
+
+
+def _code_of(text: str) -> str:
+    """C / C++ text without comments and with string literals emptied."""
+    return re.sub(r'//[^\n]*|/\*.*?\*/|"(?:\\.|[^"\\\n])*"', lambda m: '""' if m.group(0)[0] == '"' else " ", text, flags=re.S)
+
+
+def test_comparison_build_recompiles_every_user_of_the_piece_layout():
+    """The bf16 x 6 comparison library (rave_amd/build.py: build_variant, RH_X6_F16 = 0) recompiles only VARIANT_SOURCES and
+    links the product objects of the rest: a translation unit whose code depends on the piece layout (RH_X6_F16, kX6P,
+    RH_X6_NPIECE, rh_x6_frag, or an include of conv_x6_kernel.inc / conv2d_x6.hpp) left out of the list links f16-layout code
+    next to bf16-layout code.  Comments do not count (misc.hip names the macro in one)."""
+    from rave_amd import build
+    csrc = os.path.join(ROOT, "rave_amd", "csrc")
+    tokens = re.compile(r"\b(RH_X6_F16|kX6P|RH_X6_NPIECE|rh_x6_frag)\b")
+    incl = re.compile(r'^[ \t]*#[ \t]*include[ \t]*"(?:[^"]*/)?(conv_x6_kernel\.inc|conv2d_x6\.hpp)"', re.M)
+    users, comment_only = [], []
+    for s in build.SOURCES:
+        raw = open(os.path.join(csrc, s)).read()
+        code = _code_of(raw)
+        uses = bool(tokens.search(code)) or bool(incl.search(re.sub(r"/\*.*?\*/", " ", raw, flags=re.S)))
+        if uses:
+            users.append(s)
+        elif tokens.search(raw):
+            comment_only.append(s)
+    assert "misc.hip" in comment_only
+    assert {"conv2d.hip", "wgrad2d_x6.hip", "conv2d_x6.hip", "unit_x6.hip"} <= set(users)
+    missing = sorted(set(users) - set(build.VARIANT_SOURCES))
+    assert not missing, f"comparison build links the f16-layout objects of {missing}"
+    assert set(build.VARIANT_SOURCES) <= set(build.SOURCES)
