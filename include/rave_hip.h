@@ -219,6 +219,10 @@ int rh_conv1d_plan_info(const rh_conv1d_desc* d, int which, int has_bias, int ha
 /* Same question for rh_conv1d_bwd_weight_f32: 1 = wgrad_x6_kernel (bf16 matrix cores; for Conv1d it also produces the
  * bias gradient), 2 = first-layer vector-ALU kernel (weight + bias gradient in one pass), 0 = f32-input MFMA kernels. */
 int rh_conv1d_bwd_weight_kernel_family(const rh_conv1d_desc* d);
+/* Diagnostics for family 1: out4 = {waves per workgroup (4 = wgrad_x6_kernel; 3, 4, 6 or 9 with ONE workgroup tile over the
+ * whole weight tensor = wgrad_x6_wide_kernel, whose workgroups == K slices), workgroups, K slices, 1 if the input is staged once
+ * per position} of the launch rh_conv1d_bwd_weight_f32 would issue under the present RH_WGRAD_X6_* switches; zeros otherwise. */
+int rh_conv1d_bwd_weight_plan_info(const rh_conv1d_desc* d, int32_t* out4);
 
 /* dx = act'(x) * conv_bwd_data(dy) + add.   `x` is the forward input (needed when act != NONE),
  * `add` (B,c_in,l_in*inner) may be NULL (residual-branch gradient). */

@@ -747,6 +747,20 @@ extern "C" int rh_conv1d_bwd_weight_kernel_family(const rh_conv1d_desc* d) {
     return d->act != RH_ACT_SNAKE && rh_wgrad_x6_workspace(p) >= 0 ? 1 : 0;
 }
 
+bool rh_wgrad_x6_plan_info(const WgradP& w, int32_t* out4);
+
+extern "C" int rh_conv1d_bwd_weight_plan_info(const rh_conv1d_desc* d, int32_t* out4) {
+    if (!d || !out4) return RH_ERR_INVALID;
+    for (int i = 0; i < 4; ++i) out4[i] = 0;
+    if (d->batch <= 0 || rh_conv1d_bwd_weight_kernel_family(d) != 1) return RH_OK;
+    WgradP p{};
+    fill(d, &p);
+    alignas(16) static const float dummy[4] = {0.f, 0.f, 0.f, 0.f};
+    p.R = dummy; p.S = dummy;
+    (void)rh_wgrad_x6_plan_info(p, out4);
+    return RH_OK;
+}
+
 int64_t rh_wgrad_workspace(const rh_conv1d_desc* d) {
     WgradP p{};
     fill(d, &p);
