@@ -416,6 +416,35 @@ int rh_vq_ema_update_f32(const float* x, const int64_t* indices, int64_t n_vecto
 int rh_feed_batch_i16_f32(const int16_t* pcm, const int64_t* src_offset, const double* coef, const float* noise,
                           int32_t rows, int32_t n_signal, int32_t bit_depth, float* out, rh_stream_t stream);
 
+/* The same chain with the two augmentations the reference applies per item around it: RandomPitch in front of the crop
+ * (`rave train --rand_pitch lo,hi`: scripts/train.py:67,169, rave/dataset.py:233-236, rave/transforms.py:56-89 =
+ * scipy.signal.resample_poly(item, up, down, padtype='mean') of the whole stored item) and RandomMute behind Dequantize
+ * (rave/transforms.py:168-177, rave/configs/augmentations/mute.gin).  For every row r, with up / down reduced by their gcd,
+ * m = max(up, down), H = 10 m, h = the 2H + 1 doubles at taps[tap_offset] (= up * firwin(2H + 1, 1 / m, ('kaiser', 5.0))),
+ * x[k] = float32(pcm[base + k]) / 32767 for k < length and n_out = ceil(length * up / down):
+ *   p[n] = float32(mean + sum_k h[n down - k up + H] (x[k] - mean)),  k in [ceil((n down - H) / up), floor((n down + H) / up)]
+ *          and [0, length), accumulated in float64                    n in [in_point, in_point + n_signal)
+ *   y    = lfilter(coef, p) in float64 if coef[0] is not NaN;  out[r][i] = float32(y[i] + noise[r][i] / 2^bit_depth)
+ * A row with up == down is not resampled (p = x, bit-identical to rh_feed_batch_i16_f32 at src_offset = base + in_point);
+ * a row with mute != 0 is all zeros.  `mean` is the mean of x over the whole item row (padtype='mean').
+ * `rows` is the table in HOST memory, checked here: up, down in 1..19, the item inside pcm[0, pcm_samples), the window
+ * inside [0, n_out), the taps inside taps[0, n_taps) -- RH_ERR_INVALID and no launch otherwise.  `rows_dev` is the caller's
+ * copy of the same table in device memory, which the kernel reads; pcm, taps, noise and out are device memory. */
+typedef struct rh_feed_pitch_row {
+    int64_t base;       /* offset of the item row (one channel of one item) in pcm, in samples */
+    int64_t in_point;   /* crop point, in resampled samples */
+    double mean;
+    double coef[5];     /* b0, b1, b2, a1, a2; b0 = NaN skips the all-pass */
+    int32_t length;     /* samples of the stored item row */
+    int32_t up, down;
+    int32_t tap_offset; /* first tap of this row's ratio in `taps` (unused when up == down) */
+    int32_t mute;
+    int32_t reserved;
+} rh_feed_pitch_row;
+int rh_feed_batch_pitch_i16_f32(const int16_t* pcm, int64_t pcm_samples, const rh_feed_pitch_row* rows,
+                                const rh_feed_pitch_row* rows_dev, const double* taps, int32_t n_taps, const float* noise,
+                                int32_t n_rows, int32_t n_signal, int32_t bit_depth, float* out, rh_stream_t stream);
+
 /* ---- spectral distance ("next" item #1 of SURVEY.md section 8f, beside the hot path) ------------- */
 
 /* STFT framing of torchaudio.transforms.Spectrogram(center=True, pad_mode="reflect") as used by

@@ -7,11 +7,19 @@ The random draws follow the reference's distributions (uniform item / crop point
 [20, 2000] Hz at radius .99, U[0,1) dequantisation noise) but not its RNG streams; ``draws`` can be injected, which is
 how the parity test compares with scipy.signal.lfilter.  ``load_lmdb_dataset`` reads the reference's on-disk container (the
 lmdb / ``AudioExample`` store of scripts/preprocess.py, rave_amd/lmdb_reader.py) into the int16 tensor this class samples from.
+
+``rand_pitch=(lo, hi)`` adds the ``RandomPitch`` that ``rave train --rand_pitch lo,hi`` inserts in front of the crop
+(scripts/train.py:67,169, rave/dataset.py:233-236, rave/transforms.py:56-89: scipy.signal.resample_poly of the whole item by
+a random ratio up / down, padtype='mean') and ``p_mute`` the ``RandomMute`` of rave/configs/augmentations/mute.gin
+(rave/transforms.py:168-177), both in the same launch (rh_feed_batch_pitch_i16_f32): the polyphase filter is evaluated only
+for the samples inside the crop window.  ``RandomGain`` (gain.gin) needs nothing: it returns its input unchanged
+(rave/transforms.py:163).  The draws are host logic (``pitch_factors``, ``PitchTable``, ``draw_batch``) and need no GPU.
 """
 from __future__ import annotations
 
+import bisect
 import math
-from typing import Optional
+from typing import Optional, Sequence
 
 import numpy as np
 import torch
@@ -33,51 +41,205 @@ def random_angle(rng: np.random.Generator, min_f=20, max_f=8000, sr=24000) -> fl
     return 2 * math.pi * math.exp(rng.random() * (hi - lo) + lo) / sr
 
 
+def pitch_factors(max_factor: int, pitch_range: Sequence[float]):
+    """RandomPitch._get_factors (rave/transforms.py:63-75): every x / y with 1 <= x, y < max_factor, x != y, inside the range,
+    sorted; unreduced duplicates (2/3 and 4/6) are kept, since they shift what ``bisect_left`` picks."""
+    factor_list, ratio_list = [], []
+    for x in range(1, max_factor):
+        for y in range(1, max_factor):
+            if x == y:
+                continue
+            factor = x / y
+            if pitch_range[0] <= factor <= pitch_range[1]:
+                i = bisect.bisect_left(factor_list, factor)
+                factor_list.insert(i, factor)
+                ratio_list.insert(i, (x, y))
+    return factor_list, ratio_list
+
+
+def resample_taps(up: int, down: int) -> np.ndarray:
+    """The filter of scipy.signal.resample_poly(x, up, down) for a reduced ratio, in float64: up * firwin(2H + 1, 1 / m,
+    window=('kaiser', 5.0)) with m = max(up, down), H = 10 m -- a windowed sinc scaled to unit gain at DC."""
+    m = max(up, down)
+    half = 10 * m
+    t = np.arange(-half, half + 1, dtype=np.float64)
+    h = np.sinc(t / m) / m * np.kaiser(2 * half + 1, 5.0)
+    return up * (h / h.sum())
+
+
+def resampled_length(length: int, up: int, down: int) -> int:
+    return -(-length * up // down)
+
+
+class PitchTable:
+    """Host side of RandomPitch: the sorted factor / ratio lists and ONE float64 tap table for the distinct reduced ratios
+    (``offset[(up, down)]`` is where a ratio's 2H + 1 taps start)."""
+
+    def __init__(self, pitch_range: Sequence[float], p_pitch: float = .5, max_factor: int = 20):
+        self.lo, self.hi = float(pitch_range[0]), float(pitch_range[1])
+        self.p_pitch = p_pitch
+        self.factor_list, self.ratio_list = pitch_factors(max_factor, (self.lo, self.hi))
+        if not self.ratio_list:
+            raise RuntimeError(f"rand_pitch: no ratio x / y with x, y < {max_factor} inside [{self.lo}, {self.hi}]")
+        self.offset, taps, n = {}, [], 0
+        for up, down in sorted({self.reduce(r) for r in self.ratio_list}):
+            h = resample_taps(up, down)
+            self.offset[(up, down)] = n
+            taps.append(h)
+            n += len(h)
+        self.taps = np.concatenate(taps)
+
+    @staticmethod
+    def reduce(ratio):
+        g = math.gcd(*ratio)
+        return ratio[0] // g, ratio[1] // g
+
+    def pick(self, u: float, length: int, n_signal: int):
+        """RandomPitch.__call__ (rave/transforms.py:81-87) for the uniform draw ``u``."""
+        hi = min(self.hi, length / n_signal)
+        i = min(bisect.bisect_left(self.factor_list, u * (hi - self.lo) + self.lo), len(self.factor_list) - 1)
+        return self.ratio_list[i]
+
+    def shortest(self, length: int) -> int:
+        """The shortest item RandomPitch can return for stored items of ``length`` samples."""
+        return min(resampled_length(length, *self.reduce(r)) for r in self.ratio_list)
+
+
+def draw_batch(rng: np.random.Generator, n_items: int, length: int, batch: int, n_signal: int, sr: int = 44100,
+               p_mangle: float = .8, pitch: Optional[PitchTable] = None):
+    """The random draws of one minibatch: (items, in_points, angles) and, with ``pitch``, per item None or (up, down).  The
+    ratios are drawn after the other three, so without ``pitch`` the generator is consumed exactly as before; a pitched item's
+    crop point is drawn again, from [0, n_out - n_signal] (RandomCrop runs on the pitched item)."""
+    if n_signal > length:
+        raise RuntimeError("GpuBatchFeed: n_signal longer than the stored items")
+    items = rng.integers(0, n_items, batch)
+    in_points = rng.integers(0, length - n_signal + 1, batch)                           # randint(0, L - n) inclusive
+    angles = [random_angle(rng, 20, 2000, sr) if rng.random() < p_mangle else None for _ in range(batch)]
+    if pitch is None:
+        return items, in_points, angles
+    ratios = [None] * batch
+    for b in range(batch):
+        if rng.random() < pitch.p_pitch:
+            ratios[b] = pitch.pick(rng.random(), length, n_signal)
+            n_out = resampled_length(length, *pitch.reduce(ratios[b]))
+            in_points[b] = rng.integers(0, n_out - n_signal + 1)
+    return items, in_points, angles, ratios
+
+
+# mirror of ``rh_feed_pitch_row`` (include/rave_hip.h)
+ROW_DTYPE = np.dtype([("base", np.int64), ("in_point", np.int64), ("mean", np.float64), ("coef", np.float64, 5),
+                      ("length", np.int32), ("up", np.int32), ("down", np.int32), ("tap_offset", np.int32),
+                      ("mute", np.int32), ("reserved", np.int32)], align=True)
+
+
 class GpuBatchFeed:
     """``pcm``: int16 tensor (n_items, n_channels, length) on the GPU.  ``sample`` returns a (B, n_channels, n_signal)
-    float32 minibatch ready for ``RAVE.training_step``."""
+    float32 minibatch ready for ``RAVE.training_step``.  ``rand_pitch=(lo, hi)``: RandomPitch(n_signal, [lo, hi], max_factor,
+    prob=p_pitch) in front of the crop; ``p_mute``: RandomMute(p_mute) at the end of the chain (module docstring)."""
 
-    def __init__(self, pcm: torch.Tensor, sr: int = 44100, seed: int = 0, p_mangle: float = .8, bit_depth: int = 16):
+    def __init__(self, pcm: torch.Tensor, sr: int = 44100, seed: int = 0, p_mangle: float = .8, bit_depth: int = 16,
+                 rand_pitch: Optional[Sequence[float]] = None, p_pitch: float = .5, max_factor: int = 20, p_mute: float = 0.):
         if pcm.dtype != torch.int16 or pcm.dim() != 3 or not pcm.is_cuda:
             raise RuntimeError("GpuBatchFeed: pcm must be an int16 (items, channels, length) tensor on the GPU")
+        if not 0. <= p_mute <= 1.:
+            raise RuntimeError("GpuBatchFeed: p_mute must be between 0 and 1")
         self.pcm = pcm.contiguous()
-        self.sr, self.p_mangle, self.bit_depth = sr, p_mangle, bit_depth
+        self.sr, self.p_mangle, self.bit_depth, self.p_mute = sr, p_mangle, bit_depth, p_mute
         self.rng = np.random.default_rng(seed)
         self.gen = torch.Generator(device=pcm.device).manual_seed(seed)
+        self.pitch = self.taps = self.means = None
+        if rand_pitch is not None:
+            if len(rand_pitch) != 2:
+                raise RuntimeError("GpuBatchFeed: rand_pitch must be given two floats")     # rave/dataset.py:235
+            if not 2 <= max_factor <= 20:
+                raise RuntimeError("GpuBatchFeed: max_factor must be 2..20 (the kernel's filters cover up, down <= 19)")
+            self.pitch = PitchTable(rand_pitch, p_pitch, max_factor)
+            self.taps = torch.from_numpy(self.pitch.taps).to(pcm.device)
+            self._means()
+
+    def _means(self) -> np.ndarray:
+        """Mean of every (item, channel) row of int16 / 32767 (resample_poly's padtype='mean'), float64, computed on the device
+        once (at construction when ``rand_pitch`` is set: the PCM is static), a few items at a time, and kept on the host for
+        the row table."""
+        if self.means is None:
+            n_items, n_ch, length = self.pcm.shape
+            step = max(1, (1 << 24) // (n_ch * length))
+            parts = [(self.pcm[i:i + step].to(torch.float32) / 32767.0).to(torch.float64).mean(-1) for i in range(0, n_items, step)]
+            self.means = torch.cat(parts).reshape(n_items * n_ch).cpu().numpy()
+        return self.means
 
     def draw(self, batch: int, n_signal: int):
         n_items, _, length = self.pcm.shape
-        if n_signal > length:
-            raise RuntimeError("GpuBatchFeed: n_signal longer than the stored items")
-        items = self.rng.integers(0, n_items, batch)
-        in_points = self.rng.integers(0, length - n_signal + 1, batch)                  # randint(0, L - n) inclusive
-        angles = [random_angle(self.rng, 20, 2000, self.sr) if self.rng.random() < self.p_mangle else None
-                  for _ in range(batch)]
-        return items, in_points, angles
+        if self.pitch is not None and self.pitch.shortest(length) < n_signal:
+            raise RuntimeError(f"GpuBatchFeed: rand_pitch down to {self.pitch.lo} can shorten the {length}-sample items to "
+                               f"{self.pitch.shortest(length)} samples, fewer than n_signal = {n_signal}")
+        return draw_batch(self.rng, n_items, length, batch, n_signal, self.sr, self.p_mangle, self.pitch)
 
-    def sample(self, batch: int, n_signal: int, draws=None, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
-        items, in_points, angles = draws if draws is not None else self.draw(batch, n_signal)
+    def sample(self, batch: int, n_signal: int, draws=None, noise: Optional[torch.Tensor] = None, mute=None) -> torch.Tensor:
+        """``draws``: (items, in_points, angles) or (items, in_points, angles, ratios), ``ratios[b]`` = None or (up, down) and
+        ``in_points[b]`` then counted in resampled samples; ``mute``: optional mask, True = the item is silenced."""
+        if draws is None:
+            draws = self.draw(batch, n_signal)
+            if mute is None and self.p_mute > 0:
+                mute = self.rng.random(batch) < self.p_mute
+        items, in_points, angles = draws[:3]
+        ratios = draws[3] if len(draws) > 3 else None
         n_items, n_ch, length = self.pcm.shape
         rows = batch * n_ch
-        off = np.empty(rows, dtype=np.int64)
-        coef = np.full((rows, 5), np.nan, dtype=np.float64)
-        for b in range(batch):
-            for c in range(n_ch):
-                r = b * n_ch + c
-                off[r] = (int(items[b]) * n_ch + c) * length + int(in_points[b])
-                if angles[b] is not None:
-                    bb, aa = pole_to_z_filter(angles[b], .99)
-                    coef[r] = [bb[0], bb[1], bb[2], aa[1], aa[2]]
         dev = self.pcm.device
-        off_d = torch.from_numpy(off).to(dev)
-        coef_d = torch.from_numpy(coef).to(dev)
         if noise is None:
             noise = torch.rand(rows, n_signal, device=dev, generator=self.gen)
         noise = noise.to(dev, torch.float32).contiguous()
         out = torch.empty(batch, n_ch, n_signal, device=dev, dtype=torch.float32)
-        L.check(L.lib.rh_feed_batch_i16_f32(L.ptr(self.pcm), L.ptr(off_d), L.ptr(coef_d), L.ptr(noise), rows, n_signal,
-                                            self.bit_depth, L.ptr(out), L.stream()), "feed_batch")
+        pitched = ratios is not None and any(r is not None for r in ratios)
+        muted = mute is not None and any(mute)
+        if not (pitched or muted):
+            off = np.empty(rows, dtype=np.int64)
+            coef = np.full((rows, 5), np.nan, dtype=np.float64)
+            for b in range(batch):
+                for c in range(n_ch):
+                    r = b * n_ch + c
+                    off[r] = (int(items[b]) * n_ch + c) * length + int(in_points[b])
+                    if angles[b] is not None:
+                        bb, aa = pole_to_z_filter(angles[b], .99)
+                        coef[r] = [bb[0], bb[1], bb[2], aa[1], aa[2]]
+            off_d = torch.from_numpy(off).to(dev)
+            coef_d = torch.from_numpy(coef).to(dev)
+            L.check(L.lib.rh_feed_batch_i16_f32(L.ptr(self.pcm), L.ptr(off_d), L.ptr(coef_d), L.ptr(noise), rows, n_signal,
+                                                self.bit_depth, L.ptr(out), L.stream()), "feed_batch")
+            return out
+        table = np.zeros(rows, dtype=ROW_DTYPE)
+        table["coef"] = np.nan
+        table["length"] = length
+        table["up"] = table["down"] = 1
+        means = self._means() if pitched else None
+        for b in range(batch):
+            ratio = ratios[b] if ratios is not None else None
+            for c in range(n_ch):
+                row = table[b * n_ch + c]
+                row["base"] = (int(items[b]) * n_ch + c) * length
+                row["in_point"] = int(in_points[b])
+                row["mute"] = int(mute is not None and bool(mute[b]))
+                if angles[b] is not None:
+                    bb, aa = pole_to_z_filter(angles[b], .99)
+                    row["coef"] = [bb[0], bb[1], bb[2], aa[1], aa[2]]
+                if ratio is not None:
+                    row["up"], row["down"] = int(ratio[0]), int(ratio[1])
+                    row["mean"] = means[int(items[b]) * n_ch + c]
+                    row["tap_offset"] = self._tap_offset(ratio)
+        table_d = torch.from_numpy(table.view(np.uint8)).to(dev)
+        n_taps = 0 if self.taps is None else self.taps.numel()
+        L.check(L.lib.rh_feed_batch_pitch_i16_f32(L.ptr(self.pcm), self.pcm.numel(), table.ctypes.data, L.ptr(table_d),
+                                                  L.ptr(self.taps), n_taps, L.ptr(noise), rows, n_signal, self.bit_depth,
+                                                  L.ptr(out), L.stream()), "feed_batch_pitch")
         return out
+
+    def _tap_offset(self, ratio) -> int:
+        """Where the taps of ``ratio`` start in the table; 0 (never read) for a ratio that reduces to 1/1.  A ratio outside 1..19
+        or outside the table of this feed is left to the entry point's own checks, which refuse it."""
+        if self.pitch is None or min(ratio) < 1:
+            return -1
+        return self.pitch.offset.get(PitchTable.reduce(ratio), 0 if ratio[0] == ratio[1] else -1)
 
 
 def load_lmdb_dataset(db_path: str, n_channels: Optional[int] = None, audio_key: str = "waveform", device=None,

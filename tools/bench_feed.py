@@ -1,20 +1,45 @@
-"""Throughput of the GPU data feed (rave_amd/data.py): batches of 32 x 65536 from 64 resident items."""
+"""Throughput of the GPU data feed (rave_amd/data.py): batches of 32 x 65536 from 64 resident items.
+``--rand-pitch lo,hi`` adds a leg with RandomPitch on (about half the items resampled), timed in the same process."""
+import argparse
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from rave_amd import data as D
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--rand-pitch", default=None, help="lo,hi: also time the feed with RandomPitch in this range")
+ap.add_argument("--p-pitch", type=float, default=.5, help="share of the items that are resampled (reference: 0.5)")
+ap.add_argument("--reps", type=int, default=3, help="timed windows per leg, alternating between the legs")
+args = ap.parse_args()
+
 dev = torch.device("cuda:0")
 pcm = torch.randint(-20000, 20000, (64, 1, 4 * 65536), dtype=torch.int16, device=dev)
-feed = D.GpuBatchFeed(pcm, seed=0)
-for _ in range(3):
-    feed.sample(32, 65536)
+legs = [("feed", D.GpuBatchFeed(pcm, seed=0))]
+if args.rand_pitch:
+    lo, hi = map(float, args.rand_pitch.split(","))
+    legs.append((f"feed --rand-pitch {lo:g},{hi:g} (p = {args.p_pitch:g})", D.GpuBatchFeed(pcm, seed=0, rand_pitch=(lo, hi), p_pitch=args.p_pitch)))
+
+
+def window(feed, n=10):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        feed.sample(32, 65536)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n
+
+
+for _, feed in legs:
+    for _ in range(3):
+        feed.sample(32, 65536)
 torch.cuda.synchronize()
-e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-e0.record()
-n = 10
-for _ in range(n):
-    feed.sample(32, 65536)
-e1.record()
-torch.cuda.synchronize()
-ms = e0.elapsed_time(e1) / n
-print(f"feed: {ms:.3f} ms per batch of 32 x 65536 = {32 * 65536 / ms / 1e3:.1f} M samples/s (noise draw included)")
+times = {name: [] for name, _ in legs}
+for _ in range(args.reps):
+    for name, feed in legs:
+        times[name].append(window(feed))
+for name, _ in legs:
+    t = sorted(times[name])
+    ms = t[len(t) // 2]
+    print(f"{name}: {ms:.3f} ms per batch of 32 x 65536 = {32 * 65536 / ms / 1e3:.1f} M samples/s (noise draw included; "
+          f"median of {len(t)} windows of 10 batches, {t[0]:.3f} .. {t[-1]:.3f} ms)")
