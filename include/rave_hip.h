@@ -551,6 +551,23 @@ typedef struct rh_adam_item {
 int rh_adam_step_f32(const rh_adam_item* items, int32_t n_items, const float* lr, float beta1, float beta2, float eps,
                      float* aux, rh_stream_t stream);
 
+/* Exponential average of the weights over many tensors (`rave train --ema`: the EMA callback of scripts/train.py:88-102).
+ * rh_ema_update_f32 = on_train_batch_end (:88-96): for every item  a = a * f + b * g  with a = the average, b = the parameter,
+ * f = (float)factor, g = (float)(1.0 - factor) (subtraction in double) -- three separately rounded f32 operations, bit for bit
+ * what torch's `w * factor + p * (1 - factor)` gives; b is only read.
+ * rh_swap_f32 = swap_weights (:98-102): exchanges the contents of a and b in one pass, in place on both sides.
+ * `items` is a HOST array (device pointers inside) consumed during the call: the tables travel in the kernel arguments,
+ * <= 64 tensors per launch; items with n == 0 take no slot.  The whole table is checked before anything is launched:
+ * n_items < 0, a null table with n_items > 0, a null pointer in an item with n > 0, n < 0 or n >= 2^31 - 1, a == b, and a
+ * factor that is not a finite number in [0, 1] are refused with RH_ERR_INVALID; n_items == 0 launches nothing. */
+typedef struct rh_pair_item {
+    float* a;
+    float* b;
+    int64_t n;
+} rh_pair_item;
+int rh_ema_update_f32(const rh_pair_item* items, int32_t n_items, double factor, rh_stream_t stream);
+int rh_swap_f32(const rh_pair_item* items, int32_t n_items, rh_stream_t stream);
+
 /* Feature-matching distance of the GAN phase (rave/model.py:359-372 over rave/core.py:236-252, norm "L1") on UNSPLIT
  * discriminator feature maps: item i is a dense f32 tensor of 2 * half elements, the real half of the batch first;
  * distance = sum_i w_i * (relative ? sum|r-f| / sum|r| : sum|r-f|)  (the host folds the 1 / count factors -- and for the

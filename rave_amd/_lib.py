@@ -34,6 +34,11 @@ class AdamItem(C.Structure):
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64), ("step", C.c_void_p)]
 
 
+class PairItem(C.Structure):
+    """Mirror of ``rh_pair_item`` (include/rave_hip.h)."""
+    _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("n", C.c_int64)]
+
+
 class WnBwdItem(C.Structure):
     """Mirror of ``rh_wn_bwd_item`` (include/rave_hip.h)."""
     _fields_ = [("dw", C.c_void_p), ("v", C.c_void_p), ("g", C.c_void_p), ("norms", C.c_void_p), ("dv", C.c_void_p),
@@ -143,6 +148,8 @@ def _load() -> C.CDLL:
         "rh_loss_combine_fwd_f32": ([C.POINTER(LossItem), I32, P, P, P], C.c_int),
         "rh_loss_combine_bwd_f32": ([C.POINTER(LossItem), I32, P, P, P], C.c_int),
         "rh_adam_step_f32": ([C.POINTER(AdamItem), I32, P, F, F, F, P, P], C.c_int),
+        "rh_ema_update_f32": ([C.POINTER(PairItem), I32, C.c_double, P], C.c_int),
+        "rh_swap_f32": ([C.POINTER(PairItem), I32, P], C.c_int),
         "rh_x6_uses_ranges": ([], C.c_int),
         "rh_x6_range_words": ([], C.c_int),
         "rh_x6_set_ranges": ([P, P, P, P], C.c_int),

@@ -18,12 +18,12 @@
 #include <algorithm>
 #include <unordered_map>
 #include <vector>
-#include "common.hpp"
+#include "multi_tensor.hpp"
 
 namespace {
 
-constexpr int kAdamItems = 64;
-constexpr int kAdamElems = 2048;          // elements per workgroup
+constexpr int kAdamItems = kMtItems;
+constexpr int kAdamElems = kMtElems;      // elements per workgroup
 constexpr int kAdamTicks = 256;           // counters per tick launch
 
 struct AdamTable {
@@ -62,11 +62,7 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
 
 __global__ __launch_bounds__(256) void adam_update_kernel(const AdamTable tb, const float* __restrict__ lr,
                                                           const float* __restrict__ aux, float beta1, float beta2, float eps) {
-    int lo = 0, hi = tb.count - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (tb.blk_begin[mid] <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
+    RH_MT_FIND(tb, lo)
     const int n = tb.n[lo];
     const int off = ((int)blockIdx.x - tb.blk_begin[lo]) * kAdamElems;
     float* __restrict__ p = tb.p[lo];
@@ -132,24 +128,14 @@ extern "C" int rh_adam_step_f32(const rh_adam_item* items, int32_t n_items, cons
                            (double)beta2);
         if (int e = rh_check_launch("adam_tick")) return e;
     }
-    // `i` is the consumed index: empty tensors are skipped without taking a table slot, so a chunk may span more than
-    // kAdamItems items -- the next chunk continues where this one stopped (never re-processing an item)
+    // empty tensors take no table slot, a chunk continues where the last one stopped (rh_mt_fill)
     for (int i = 0; i < n_items;) {
         AdamTable tb;
-        int cnt = 0, blk = 0;
-        for (; i < n_items && cnt < kAdamItems; ++i) {
-            const rh_adam_item& it = items[i];
-            if (it.n == 0) continue;
-            tb.p[cnt] = it.p; tb.g[cnt] = it.g; tb.m[cnt] = it.m; tb.v[cnt] = it.v;
-            tb.n[cnt] = (int)it.n;
-            tb.slot[cnt] = slot[(size_t)i];
-            tb.blk_begin[cnt] = blk;
-            blk += (int)((it.n + kAdamElems - 1) / kAdamElems);
-            ++cnt;
-        }
-        if (cnt == 0) continue;
-        tb.blk_begin[cnt] = blk;
-        tb.count = cnt;
+        const int blk = rh_mt_fill(tb, items, n_items, i, [&](AdamTable& t, int c, const rh_adam_item& it, int idx) {
+            t.p[c] = it.p; t.g[c] = it.g; t.m[c] = it.m; t.v[c] = it.v;
+            t.slot[c] = slot[(size_t)idx];
+        });
+        if (blk == 0) continue;
         hipLaunchKernelGGL(adam_update_kernel, dim3((unsigned)blk), dim3(256), 0, (hipStream_t)stream, tb, lr, (const float*)aux, beta1,
                            beta2, eps);
         if (int e = rh_check_launch("adam_update")) return e;
