@@ -11,6 +11,10 @@
  *   - tensors are contiguous fp32, layout (B, C, L) with L innermost (PyTorch default);
  *   - every pointer is a DEVICE pointer owned by the caller (the PyTorch caching allocator in
  *     the Python binding); the library never allocates, frees or synchronises;
+ *   - alignment: activations, gradients, parameters and optimizer state may sit at any 4-byte aligned address (the
+ *     kernels pick 16-byte paths only where the pointers allow them).  Buffers the caller allocates FOR the library --
+ *     packed weights, workspaces, range slots -- are expected 16-byte aligned: rh_residual_unit_fwd_f32 refuses misaligned
+ *     packed weights (RH_ERR_INVALID), the convolution entry points take a slower kernel or run unsplit instead;
  *   - `stream` is a hipStream_t passed as void*; all work is enqueued on it;
  *   - return value: RH_OK (0), <0 = invalid / unsupported argument (nothing enqueued),
  *     >0 = hipError_t of the failed launch; rh_last_error() gives a thread-local message;
@@ -183,7 +187,8 @@ int rh_conv1d_kernel_family(const rh_conv1d_desc* d, int which, int has_bias, in
  * (rave/blocks.py:31-45 `Residual`, :83-112 `DilatedUnit`; C = 32 / 64 / 96, stride 1, "same" padding, no biases).
  * d3 / d1 describe the two convolutions (act / act_slope = the activation in front of each), wp3_fwd / wp1_fwd are
  * their packed forward operands.  h: receives the intermediate for the backward pass, or NULL (inference: never
- * written).  Results are bit-identical to rh_conv1d_fwd_f32(d3) followed by rh_conv1d_fwd_f32(d1, residual = x). */
+ * written).  Results are bit-identical to rh_conv1d_fwd_f32(d3) followed by rh_conv1d_fwd_f32(d1, residual = x).
+ * wp3_fwd / wp1_fwd must be 16-byte aligned (x: 4-byte, as everywhere): RH_ERR_INVALID otherwise, nothing enqueued. */
 int rh_residual_unit_fused(const rh_conv1d_desc* d3, const rh_conv1d_desc* d1);   /* 1 = the pair fits the fused launch */
 int rh_residual_unit_fwd_f32(const rh_conv1d_desc* d3, const rh_conv1d_desc* d1, const float* x, const float* wp3_fwd,
                              const float* wp1_fwd, float* h, float* y, rh_stream_t stream);
