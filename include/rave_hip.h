@@ -573,6 +573,38 @@ typedef struct rh_pair_item {
 int rh_ema_update_f32(const rh_pair_item* items, int32_t n_items, double factor, rh_stream_t stream);
 int rh_swap_f32(const rh_pair_item* items, int32_t n_items, rh_stream_t stream);
 
+/* The recurrent latent layer (rave/blocks.py:295-319 `GRU`: torch.nn.GRU(input_size = H, hidden_size = H, num_layers = L,
+ * batch_first = True) between two permute(0, 2, 1), h0 = 0; placed in front of the v2 decoder by configs/hybrid.gin, :632-633).
+ * x, y, dy, dx are the model's (batch, hidden, t_len) tensors, time innermost: the permutes are addressing, no transposed
+ * copy is made.  Gates in torch's order (r, z, n); w_ih / w_hh are (3H, H), b_ih / b_hh (3H): the layouts of
+ * gru.weight_ih_l{k} etc.  f32 throughout; the sigmoid is 1 / (1 + expf(-a)): finite, and exactly 0 / 1 at a = -+100.
+ * Every reduction has one fixed order (no atomics): results are bit-identical from run to run.
+ * Sizes: hidden a multiple of 16 in [16, 128], 1 <= layers <= 4 (rh_gru_supported answers 1 / 0), batch >= 1, t_len >= 1,
+ * batch * (t_len + 1) < 2^22 -- anything else is RH_ERR_UNSUPPORTED; null pointers are RH_ERR_INVALID, a short workspace
+ * RH_ERR_WORKSPACE; nothing is enqueued in any of these cases.
+ * `layers` is a HOST array of n_layers items (device pointers inside) consumed during the call; fwd reads the four
+ * parameters of each, bwd also writes the four gradients (overwritten, not accumulated).
+ * Workspace: rh_gru_workspace_bytes(..., training, &bytes), any 4-byte aligned device buffer.  With training != 0 fwd leaves in
+ * it what bwd needs (per layer and step: r, z, n, W_hn h + b_hn, h) and bwd must be given the SAME buffer, unmodified,
+ * with the same x and sizes; its tail is scratch of both.  With training == 0 nothing is kept (4 * batch * t_len * hidden
+ * floats of scratch, roughly). */
+typedef struct rh_gru_item {
+    const float* w_ih;
+    const float* w_hh;
+    const float* b_ih;
+    const float* b_hh;
+    float* dw_ih; /* the four gradients: bwd only, fwd ignores them */
+    float* dw_hh;
+    float* db_ih;
+    float* db_hh;
+} rh_gru_item;
+int rh_gru_supported(int32_t hidden, int32_t layers);
+int rh_gru_workspace_bytes(int32_t batch, int32_t hidden, int32_t t_len, int32_t layers, int32_t training, int64_t* bytes);
+int rh_gru_fwd_f32(const float* x, const rh_gru_item* layers, int32_t n_layers, int32_t batch, int32_t hidden, int32_t t_len,
+                   int32_t training, float* y, void* workspace, int64_t workspace_bytes, rh_stream_t stream);
+int rh_gru_bwd_f32(const float* dy, const float* x, const rh_gru_item* layers, int32_t n_layers, int32_t batch, int32_t hidden,
+                   int32_t t_len, float* dx, void* workspace, int64_t workspace_bytes, rh_stream_t stream);
+
 /* Feature-matching distance of the GAN phase (rave/model.py:359-372 over rave/core.py:236-252, norm "L1") on UNSPLIT
  * discriminator feature maps: item i is a dense f32 tensor of 2 * half elements, the real half of the batch first;
  * distance = sum_i w_i * (relative ? sum|r-f| / sum|r| : sum|r-f|)  (the host folds the 1 / count factors -- and for the

@@ -39,6 +39,11 @@ class PairItem(C.Structure):
     _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("n", C.c_int64)]
 
 
+class GruItem(C.Structure):
+    """Mirror of ``rh_gru_item`` (include/rave_hip.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("w_ih", "w_hh", "b_ih", "b_hh", "dw_ih", "dw_hh", "db_ih", "db_hh")]
+
+
 class WnBwdItem(C.Structure):
     """Mirror of ``rh_wn_bwd_item`` (include/rave_hip.h)."""
     _fields_ = [("dw", C.c_void_p), ("v", C.c_void_p), ("g", C.c_void_p), ("norms", C.c_void_p), ("dv", C.c_void_p),
@@ -150,6 +155,10 @@ def _load() -> C.CDLL:
         "rh_adam_step_f32": ([C.POINTER(AdamItem), I32, P, F, F, F, P, P], C.c_int),
         "rh_ema_update_f32": ([C.POINTER(PairItem), I32, C.c_double, P], C.c_int),
         "rh_swap_f32": ([C.POINTER(PairItem), I32, P], C.c_int),
+        "rh_gru_supported": ([I32, I32], C.c_int),
+        "rh_gru_workspace_bytes": ([I32, I32, I32, I32, I32, C.POINTER(I64)], C.c_int),
+        "rh_gru_fwd_f32": ([P, C.POINTER(GruItem), I32, I32, I32, I32, I32, P, P, I64, P], C.c_int),
+        "rh_gru_bwd_f32": ([P, P, C.POINTER(GruItem), I32, I32, I32, I32, P, P, I64, P], C.c_int),
         "rh_x6_uses_ranges": ([], C.c_int),
         "rh_x6_range_words": ([], C.c_int),
         "rh_x6_set_ranges": ([P, P, P, P], C.c_int),

@@ -9,6 +9,7 @@ own HIP kernel.
 """
 from __future__ import annotations
 
+import math
 from typing import Callable, Optional, Sequence, Union
 
 import numpy as np
@@ -329,6 +330,51 @@ class NoiseGeneratorV2(nn.Module):
             noise = torch.rand_like(ir) * 2 - 1
         out = fft_convolve(noise, ir).permute(0, 2, 1, 3)
         return out.reshape(out.shape[0], out.shape[1], -1)
+
+
+class _GRUWeights(nn.Module):
+    """The parameters of ``torch.nn.GRU(hidden, hidden, num_layers)`` under its names, created and initialised in its order
+    (torch/nn/modules/rnn.py: per layer weight_ih, weight_hh, bias_ih, bias_hh; every one U(-1/sqrt(hidden), 1/sqrt(hidden)),
+    drawn in registration order), so that the same seed gives the same values.  A holder only: torch.nn.GRU itself would
+    re-lay its weights for MIOpen when moved to the GPU."""
+
+    def __init__(self, hidden: int, num_layers: int) -> None:
+        super().__init__()
+        for k in range(num_layers):
+            for name, shape in ((f"weight_ih_l{k}", (3 * hidden, hidden)), (f"weight_hh_l{k}", (3 * hidden, hidden)),
+                                (f"bias_ih_l{k}", (3 * hidden,)), (f"bias_hh_l{k}", (3 * hidden,))):
+                self.register_parameter(name, nn.Parameter(torch.empty(shape)))
+        stdv = 1.0 / math.sqrt(hidden) if hidden > 0 else 0
+        for w in self.parameters():
+            nn.init.uniform_(w, -stdv, stdv)
+
+
+class GRU(nn.Module):
+    """rave/blocks.py:295-319: the recurrent layer configs/hybrid.gin puts in front of the v2 decoder, on the HIP kernels of
+    csrc/gru.hip (forward and backward through time on the (B, C, T) tensor itself: no permute).  Same constructor, same
+    ``state_dict`` keys (gru.weight_ih_l{k}, gru.weight_hh_l{k}, gru.bias_ih_l{k}, gru.bias_hh_l{k}, gru_state) and the same
+    initial values under the same seed as the reference's module: checkpoints go both ways."""
+
+    def __init__(self, latent_size: int, num_layers: int) -> None:
+        super().__init__()
+        if not ops.gru_supported(latent_size, num_layers):
+            raise NotImplementedError(f"rave_amd GRU: latent_size {latent_size} x {num_layers} layers is not built "
+                                      "(latent_size: a multiple of 16 in [16, 128]; num_layers: 1..4)")
+        self.gru = _GRUWeights(latent_size, num_layers)
+        self.num_layers = num_layers
+        self.register_buffer("gru_state", torch.tensor(0))
+        self.enabled = True
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if not self.enabled:
+            return x
+        return ops.gru(x, list(self.gru.parameters()), self.num_layers)
+
+    def disable(self):
+        self.enabled = False
+
+    def enable(self):
+        self.enabled = True
 
 
 class EncoderV2(nn.Module):

@@ -705,13 +705,15 @@ def build_v2(n_channels: int = 1, capacity: int = 96, ratios=(4, 4, 4, 2), laten
              noise: bool = False, update_discriminator_every: int = 4, discriminator_kind: str = "v2",
              encoder_kind: str = "variational", noise_augmentation: int = 0, num_quantizers: int = 16,
              codebook_size: int = 1024, log_epsilon: float = 1e-7, num_skipped_features: int = 1,
-             spectral_capacity: int = 32) -> RAVE:
+             spectral_capacity: int = 32, gru_layers: int = 0) -> RAVE:
     """configs/v1.gin + configs/v2.gin transcribed (cf. oracle/ref_models.py for the citations).
     ``snake`` / ``adain`` add the generator-side overlays of configs/v3.gin (snake.gin: every activation
     -> blocks.Snake; adain.gin: AdaptiveInstanceNormalization before every unit); ``causal`` =
     configs/causal.gin.  ``discriminator_kind``: "v2" (MPD + MSD, v2.gin:53-75), "descript"
     (descript_discriminator.gin), "spectral" (spectral_discriminator.gin: MSD + Encodec STFT nets).
-    ``encoder_kind``: "variational" or "discrete" (discrete.gin: EncoderV2(n_out=1) + RVQ + noise channels)."""
+    ``encoder_kind``: "variational" or "discrete" (discrete.gin: EncoderV2(n_out=1) + RVQ + noise channels).
+    ``gru_layers`` > 0 puts blocks.GRU in front of the decoder (the generator half of configs/hybrid.gin:33-38; its mel
+    encoder input is not provided)."""
     cc.set_default_padding_mode("causal" if causal else "centered")
     blocks.set_normalization_mode("weight_norm")
     dil = dilations or V2_DILATIONS
@@ -741,6 +743,8 @@ def build_v2(n_channels: int = 1, capacity: int = 96, ratios=(4, 4, 4, 2), laten
                                               ratios=[2, 2, 2], noise_bands=32))
     else:
         extra_dec = {}
+    if gru_layers > 0:
+        extra_dec["recurrent_layer"] = partial(blocks.GRU, num_layers=gru_layers)
     dec = partial(blocks.GeneratorV2, data_size=n_band, capacity=capacity, ratios=ratios,
                   latent_size=dec_latent, kernel_size=3, dilations=dil, amplitude_modulation=True, **extra,
                   **extra_dec)

@@ -1386,6 +1386,69 @@ def snake(x: Tensor, alpha: Tensor) -> Tensor:
     return _SnakeFn.apply(x, alpha)
 
 
+def gru_supported(hidden: int, num_layers: int) -> bool:
+    return L.lib.rh_gru_supported(int(hidden), int(num_layers)) == 1
+
+
+def _gru_items(params, grads, n_layers: int):
+    items = (L.GruItem * n_layers)()
+    for k in range(n_layers):
+        it = items[k]
+        it.w_ih, it.w_hh, it.b_ih, it.b_hh = (L.ptr(p) for p in params[4 * k:4 * k + 4])
+        if grads is not None:
+            it.dw_ih, it.dw_hh, it.db_ih, it.db_hh = (L.ptr(g) for g in grads[4 * k:4 * k + 4])
+    return items
+
+
+class _GruFn(torch.autograd.Function):
+    """torch.nn.GRU(H, H, num_layers, batch_first=True) between two permute(0, 2, 1), h0 = 0 (rave/blocks.py:295-319), on the
+    (B, H, T) tensor itself: rh_gru_fwd_f32 / rh_gru_bwd_f32.  ``params``: weight_ih, weight_hh, bias_ih, bias_hh per layer.
+    The output carries no range slot (the recurrence has no epilogue that sees the whole tensor): a convolution that
+    consumes it takes its rh_amax_f32 pass in _range_of, one small launch on a (B, latent, T) tensor."""
+
+    @staticmethod
+    def forward(ctx, x, n_layers, *params):
+        if len(params) != 4 * n_layers:
+            raise ValueError(f"rave_amd gru: {len(params)} parameter tensors for {n_layers} layers (4 per layer)")
+        ctx.slots = tuple(_slot_of(p) for p in params)
+        x = _chk(x, "x")
+        params = tuple(_chk(p, "GRU parameter") for p in params)
+        b, h, t = x.shape
+        for k in range(n_layers):
+            for p, shape in zip(params[4 * k:4 * k + 4], ((3 * h, h), (3 * h, h), (3 * h,), (3 * h,))):
+                if tuple(p.shape) != shape:
+                    raise ValueError(f"rave_amd gru: layer {k} parameter of shape {tuple(p.shape)}, expected {shape}")
+        training = int(any(ctx.needs_input_grad))
+        nbytes = C.c_int64(0)
+        L.check(L.lib.rh_gru_workspace_bytes(b, h, t, n_layers, training, C.byref(nbytes)), "gru_workspace_bytes")
+        ws = torch.empty(nbytes.value // 4, device=x.device, dtype=torch.float32)
+        y = torch.empty_like(x)
+        L.check(L.lib.rh_gru_fwd_f32(L.ptr(x), _gru_items(params, None, n_layers), n_layers, b, h, t, training, L.ptr(y),
+                                     L.ptr(ws), nbytes.value, L.stream()), "gru_fwd")
+        if training:
+            ctx.save_for_backward(x, ws, *params)
+            ctx.n_layers = n_layers
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, ws, *params = ctx.saved_tensors
+        dy = _chk(dy, "dy")
+        b, h, t = x.shape
+        # parameter gradients go straight into the data-parallel reducer's bucket views where it has installed them
+        grads = [_grad_out(slot if need else None, p.shape, x.device)
+                 for slot, p, need in zip(ctx.slots, params, ctx.needs_input_grad[2:])]
+        dx = torch.empty_like(x)
+        L.check(L.lib.rh_gru_bwd_f32(L.ptr(dy), L.ptr(x), _gru_items(params, grads, ctx.n_layers), ctx.n_layers, b, h, t,
+                                     L.ptr(dx), L.ptr(ws), ws.numel() * 4, L.stream()), "gru_bwd")
+        return (dx if ctx.needs_input_grad[0] else None, None,
+                *[g if need else None for g, need in zip(grads, ctx.needs_input_grad[2:])])
+
+
+def gru(x: Tensor, params, num_layers: int) -> Tensor:
+    return _GruFn.apply(x, num_layers, *params)
+
+
 class _AdainTransferFn(torch.autograd.Function):
     """(x - mean_x) / (std_x + 1e-5) * std_y + mean_y with per-(batch item, channel) statistics (rave/blocks.py:887-895).
     Backward = the same kernel on dy with zero means (d/dx = std_y / (std_x + 1e-5); the statistics are buffers)."""
