@@ -13,14 +13,19 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib as L
+from ._arming import armed_call, drop as _drop_armed
 from ._lib import ACT_LEAKY, ACT_NONE, ACT_SNAKE  # noqa: F401
+from ._ranges import (_RANGE_POOLS, _RANGE_WORDS, _RANGES, _attach_range, _new_range, _range_of, _ranges_on,  # noqa: F401
+                      _reattach_range, _valid_slot, range_capture_end, range_miss_log_begin, range_miss_log_end, range_reset)
+from ._side import (SIDE, _WN_BATCH_MAX, _OnSide, _note_use, _reduce_batch, _side_enabled, _side_stream, _single_use,  # noqa: F401
+                    _wn_batch_enabled, abandon_side_streams, join_side_streams, side_stream_for_collective)
 
 Tensor = torch.Tensor
 
 
 # ---- optional per-launch timing (bench.py roofline leg) -------------------------------------------------------------
 # Two clocks per launch: (a) the MAIN kernel's own start / stop timestamps -- the library dispatches it with a pair of HIP
-# events attached (rh_set_kernel_events -> hipExtLaunchKernelGGL), i.e. the duration rocprofv3 reports for that dispatch;
+# events attached (_arming.armed_call(events=...) -> hipExtLaunchKernelGGL), i.e. the duration rocprofv3 reports for that dispatch;
 # (b) a torch event bracket on the launch stream around the whole C-ABI call (main kernel + its split-K finalize /
 # partial-sum reduction launches + event overhead).
 _PROFILE = None
@@ -64,8 +69,7 @@ def _timed(kind, f, b, fn):
     e0 = torch.cuda.Event(enable_timing=True)
     e1 = torch.cuda.Event(enable_timing=True)
     e0.record()
-    L.lib.rh_set_kernel_events(h0, h1)
-    r = fn()
+    r = armed_call(fn, events=(h0, h1))
     used = L.lib.rh_kernel_events_used()
     e1.record()
     _PROFILE.append((kind, f, b, e0, e1, h0, h1, used))
@@ -121,13 +125,11 @@ def _rel(a: Tensor, b: Tensor) -> float:
 
 class _ExactF32:
     def __enter__(self):
-        import os
         self.old = {k: os.environ.get(k) for k in ("RH_CONV_X6", "RH_WGRAD_X6")}
         os.environ["RH_CONV_X6"] = "0"
         os.environ["RH_WGRAD_X6"] = "0"
 
     def __exit__(self, *a):
-        import os
         for k, v in self.old.items():
             if v is None:
                 os.environ.pop(k, None)
@@ -243,172 +245,6 @@ def _ws(nbytes: int, device) -> Optional[Tensor]:
     return torch.empty(nbytes // 4, device=device, dtype=torch.float32) if nbytes > 0 else None
 
 
-# ---- range slots of the f16 matrix-core kernels (include/rave_hip.h: rh_x6_set_ranges; csrc/common.hpp: RH_X6_F16) ------------
-# The x6 kernels scale every activation operand by a power of two derived from the TENSOR's max |x|.  That maximum travels with
-# the tensor as a "range slot" (kRangeWords uint32 in device memory): the kernel that produces a tensor leaves it there
-# (epilogue atomicMax: no extra pass), and the tensor OBJECT carries the slot as an attribute together with its version
-# counter.  A tensor without a (current) slot -- produced by a torch op, a view, modified in place -- gets one from a pass of
-# rh_amax_f32 the first time a convolution consumes it.  Slots come from a zeroed pool; RAVE.training_step takes a fresh pool per
-# step (range_reset: one fill launch -- recorded into a hipGraph it re-zeroes the slots at every replay, so a replayed step
-# computes the same scales as an eager one).  A pool taken inside a capture belongs to the graph (every replay re-zeroes it): eager
-# work after the capture never takes a slot from it (_new_range starts a fresh pool; GraphedTrainingStep also drops it from the
-# table when the recording ends and keeps it alive with the graph, range_capture_end).
-_RANGES = L.lib.rh_x6_uses_ranges() == 1
-_RANGE_WORDS = L.lib.rh_x6_range_words()
-_RANGE_SLOTS = 2048     # 4 KB each: more than any step of the shipped configs uses (a pool that runs out mid-step is replaced)
-_RANGE_POOLS = {}        # device -> [pool, cursor, previous pool (kept alive: a side stream may still read it), stream of the reset,
-#                                     taken inside a stream capture]
-
-
-def range_reset(device=None, _exhausted: bool = False) -> None:
-    """Start a fresh zeroed slot pool (call at the start of a step; mandatory inside a hipGraph capture)."""
-    if not _RANGES:
-        return
-    for dev in ([device] if device is not None else list(_RANGE_POOLS)):
-        st = _RANGE_POOLS.get(dev)
-        prev = st[0] if st else None
-        cur = torch.cuda.current_stream(dev)
-        pool = torch.zeros(_RANGE_SLOTS * _RANGE_WORDS, device=dev, dtype=torch.int32)
-        if _exhausted:
-            # a pool that ran out in the middle of a step, possibly on the weight-gradient side stream: the other stream of the
-            # step must not publish into the new pool before its zero fill has run
-            ev = torch.cuda.Event()
-            ev.record(cur)
-            d_ = dev if isinstance(dev, torch.device) else torch.device(dev)
-            for other in [st[3] if st else None, _SIDE.get(d_.index if d_.index is not None else torch.cuda.current_device())]:
-                if other is not None and other != cur:
-                    other.wait_event(ev)
-            main = st[3] if st else cur
-        else:
-            main = cur
-        _RANGE_POOLS[dev] = [pool, 0, prev, main, torch.cuda.is_current_stream_capturing()]
-
-
-def range_capture_end(device=None) -> list:
-    """Call when a stream capture has ended (successfully or not): the pools taken inside it are dropped from the table, so that
-    no later eager launch takes a slot that the graph's replays re-zero (or, before the first replay, that was never zeroed).
-    Returns them: the caller keeps them alive as long as the graph exists."""
-    out = []
-    for dev in ([device] if device is not None else list(_RANGE_POOLS)):
-        st = _RANGE_POOLS.get(dev)
-        if st is not None and st[4]:
-            out += [t for t in (st[0], st[2]) if t is not None]
-            del _RANGE_POOLS[dev]
-    return out
-
-
-def _ranges_on() -> bool:
-    return _RANGES and os.environ.get("RH_CONV_X6", "1") != "0"
-
-
-def _new_range(device) -> Tensor:
-    st = _RANGE_POOLS.get(device)
-    if st is not None and st[4] and not torch.cuda.is_current_stream_capturing():
-        range_reset(device)           # the pool of a finished capture (range_capture_end was not called): never handed out eagerly
-        st = _RANGE_POOLS[device]
-    if st is None or st[1] >= _RANGE_SLOTS:
-        range_reset(device, _exhausted=st is not None)
-        st = _RANGE_POOLS[device]
-    i = st[1]
-    st[1] = i + 1
-    return st[0][i * _RANGE_WORDS:(i + 1) * _RANGE_WORDS]
-
-
-def _attach_range(t: Optional[Tensor], slot: Optional[Tensor]) -> None:
-    if t is not None and slot is not None:
-        t._rh_range = (slot, t._version)
-
-
-def _disarm() -> None:
-    """Drop whatever rh_x6_set_ranges / rh_defer_reduce armed for the next call of this thread."""
-    L.lib.rh_x6_set_ranges(None, None, None, None)
-    L.lib.rh_defer_reduce(None)
-
-
-def _armed_call(fn):
-    """Decorator of the functions that arm the thread-local state of the library and then make the C call that consumes it:
-    if anything raises in between, the state is dropped (it would otherwise reach the next, unrelated call of the thread)."""
-    def wrapped(*a, **k):
-        try:
-            return fn(*a, **k)
-        except BaseException:
-            _disarm()
-            raise
-    return wrapped
-
-
-_RANGE_MISS = None       # diagnostics (range_miss_log_begin): [(tag, shape)] of the tensors that needed an rh_amax_f32 pass
-
-
-def range_miss_log_begin() -> None:
-    global _RANGE_MISS
-    _RANGE_MISS = []
-
-
-def range_miss_log_end():
-    global _RANGE_MISS
-    out, _RANGE_MISS = _RANGE_MISS, None
-    return out
-
-
-def _stream_of(handle, device) -> torch.cuda.Stream:
-    cur = torch.cuda.current_stream(device)
-    if cur.cuda_stream == handle:
-        return cur
-    for st in _SIDE.values():
-        if st.cuda_stream == handle:
-            return st
-    return torch.cuda.ExternalStream(handle, device=device)
-
-
-def _valid_slot(t: Tensor, s):
-    """The slot attached to ``t`` if it is current, for a consumer on stream ``s``.  A slot that rh_amax_f32 filled on ANOTHER
-    stream (the weight-gradient side stream, _arm_wgrad_ranges under _OnSide) carries the event recorded right behind that pass:
-    a consumer on a different stream waits for it (for the pass only, not for the weight-gradient kernels queued after it).
-    Such a slot filled inside a stream capture is not used outside it (and vice versa: an eager one inside a capture needs no
-    wait -- the pass was queued before the recording)."""
-    r = getattr(t, "_rh_range", None)
-    if r is None or r[1] != t._version or r[0].device != t.device:
-        return None
-    if len(r) > 2 and r[2][0] != s:
-        _, captured, ev = r[2]
-        now = torch.cuda.is_current_stream_capturing()
-        if captured and not now:
-            return None
-        if captured == now:
-            _stream_of(s, t.device).wait_event(ev)
-    return r[0]
-
-
-def _range_of(t: Tensor, s, tag: str = "") -> Tensor:
-    """The range slot of ``t``: the one its producer left -- also through a view that covers the whole producer tensor (same
-    elements, same maximum; views share the version counter) --, else computed now (one pass over ``t`` on stream ``s``).
-    The contract rests on the version counter: a write that bypasses it -- through ``.data``, or raw (ctypes / C ABI) writes
-    into an existing tensor -- leaves a stale slot behind and is outside it (a bigger stale maximum costs accuracy, a smaller
-    one overflows the f16 pieces)."""
-    slot = _valid_slot(t, s)
-    if slot is not None:
-        return slot
-    base = t._base
-    if base is not None and base.numel() == t.numel():
-        slot = _valid_slot(base, s)
-        if slot is not None:
-            t._rh_range = (slot, t._version) + tuple(base._rh_range[2:])
-            return slot
-    if _RANGE_MISS is not None:
-        _RANGE_MISS.append((tag, tuple(t.shape)))
-    slot = _new_range(t.device)
-    L.check(L.lib.rh_amax_f32(L.ptr(t), t.numel(), L.ptr(slot), s), "amax")
-    _attach_range(t, slot)
-    side = next((st for st in _SIDE.values() if st.cuda_stream == s), None)
-    if side is not None:
-        # filled on the side stream: a consumer on the compute stream must not read it before this pass has run (_valid_slot)
-        ev = torch.cuda.Event()
-        ev.record(side)
-        t._rh_range = (slot, t._version, (s, torch.cuda.is_current_stream_capturing(), ev))
-    return slot
-
-
 def _fwd(d, x, wp, bias, alpha, residual, y, s):
     _log_plan(d, 0, bias is not None, residual is not None)
     ws = _ws(L.lib.rh_conv1d_fwd_workspace_bytes(C.byref(d)), y.device)
@@ -419,12 +255,10 @@ def _fwd(d, x, wp, bias, alpha, residual, y, s):
             rin = _range_of(x, s, "fwd x")
         rout = _new_range(y.device)
 
-    @_armed_call
     def run(out, ranges=True):
-        if ranges and rout is not None:
-            L.lib.rh_x6_set_ranges(None, L.ptr(rin), L.ptr(rout), None)
-        return L.lib.rh_conv1d_fwd_f32(C.byref(d), L.ptr(x), L.ptr(wp), L.ptr(bias), L.ptr(alpha), L.ptr(residual), L.ptr(out),
-                                       L.ptr(ws), ws.numel() * 4 if ws is not None else 0, s)
+        return armed_call(lambda: L.lib.rh_conv1d_fwd_f32(C.byref(d), L.ptr(x), L.ptr(wp), L.ptr(bias), L.ptr(alpha), L.ptr(residual),
+                                                          L.ptr(out), L.ptr(ws), ws.numel() * 4 if ws is not None else 0, s),
+                          in_b=rin if ranges else None, out=rout if ranges else None)
 
     rc = _launch("conv_fwd", d, lambda: run(y), bias is not None, residual is not None)
     if rc == 0:
@@ -440,11 +274,9 @@ def _unit_fwd(d3, d1, x, wp3, wp1, h, y, s):
         rin, ry = _range_of(x, s, "unit x"), _new_range(x.device)
         rh = _new_range(x.device) if h is not None else None
 
-    @_armed_call
     def run(o_y, o_h):
-        if rin is not None:
-            L.lib.rh_x6_set_ranges(None, L.ptr(rin), L.ptr(ry), L.ptr(rh))
-        return L.lib.rh_residual_unit_fwd_f32(C.byref(d3), C.byref(d1), L.ptr(x), L.ptr(wp3), L.ptr(wp1), L.ptr(o_h), L.ptr(o_y), s)
+        return armed_call(lambda: L.lib.rh_residual_unit_fwd_f32(C.byref(d3), C.byref(d1), L.ptr(x), L.ptr(wp3), L.ptr(wp1), L.ptr(o_h),
+                                                                 L.ptr(o_y), s), in_b=rin, out=ry, out2=rh)
 
     if _PLAN_LOG is not None:
         _PLAN_LOG.append((2, (d3.c_in, d3.c_out, d3.kernel, d3.stride, d3.dilation, d3.l_in, d3.transposed), (3, d3.c_in // 32, 2, 1, 1, 1, 0, 0)))
@@ -484,12 +316,10 @@ def _dgrad(d, dy, wp, x, alpha, add, dx, s):
             rin = _range_of(dy, s, "dgrad dy")
         rout = _new_range(dx.device)
 
-    @_armed_call
     def run(out, ranges=True):
-        if ranges and rout is not None:
-            L.lib.rh_x6_set_ranges(None, L.ptr(rin), L.ptr(rout), None)
-        return L.lib.rh_conv1d_bwd_data_f32(C.byref(d), L.ptr(dy), L.ptr(wp), L.ptr(x), L.ptr(alpha), L.ptr(add), L.ptr(out),
-                                            L.ptr(ws), ws.numel() * 4 if ws is not None else 0, s)
+        return armed_call(lambda: L.lib.rh_conv1d_bwd_data_f32(C.byref(d), L.ptr(dy), L.ptr(wp), L.ptr(x), L.ptr(alpha), L.ptr(add),
+                                                               L.ptr(out), L.ptr(ws), ws.numel() * 4 if ws is not None else 0, s),
+                          in_b=rin if ranges else None, out=rout if ranges else None)
 
     rc = _launch("conv_dgrad", d, lambda: run(dx), False, add is not None)
     if rc == 0:
@@ -498,259 +328,25 @@ def _dgrad(d, dy, wp, x, alpha, add, dx, s):
     return rc
 
 
-# ---- weight-gradient branch on a side stream -----------------------------------------------------------------------------
-# In the backward pass the weight-gradient branch of a layer (wgrad kernel -> ordered reduction of its K-slice partials ->
-# weight-norm backward: one MFMA kernel with a bandwidth-bound store tail, then two small bandwidth-bound kernels -- the
-# last of them collected over all layers of the branch into one launch at the join, _WN_PENDING below) only
-# feeds the optimizer, while the data-gradient chain is what the next layer waits for.  The branch (RH_BWD_SIDE_STREAM=0
-# disables) is enqueued on a second HIP stream: it forks after the kernels that produce its operands and is joined back (a) at the
-# end of the backward pass (autograd final callback) and (b) before a data-parallel bucket leaves (rave_amd.ddp).  Recorded
-# into the step's hipGraph the two streams become parallel branches of the graph.
-_SIDE = {}
-_SIDE_PENDING = [None]
-_SIDE_HOLD = []        # incoming gradient tensors the branch still reads (see _OnSide): released when the branch is joined
-
-
-def _side_enabled() -> bool:
-    import os
-    return os.environ.get("RH_BWD_SIDE_STREAM", "1") != "0"
-
-
-def _side_stream(device):
-    """The stream of the weight-gradient branch of the backward pass (one per device)."""
-    k = device.index if device.index is not None else torch.cuda.current_device()
-    st = _SIDE.get(k)
-    if st is None:
-        st = _SIDE[k] = torch.cuda.Stream(device=device)
-    return st
-
-
-# Weight-norm backward of the layers whose weight gradient ran on the side stream: collected here and run as ONE launch
-# (rh_weight_norm_bwd_batched_f32) when the branch is joined -- at the end of the backward pass or when a data-parallel
-# bucket leaves -- instead of one 4-6 us latency-bound launch per layer (56 per v2 step).  The dv / dg tensors handed to
-# autograd are filled by that launch: like every gradient of the side stream they are valid once the branch is joined.
-# RH_WN_BATCH=0: one launch per layer, at once.
-_WN_PENDING = []
-import os as _os
-_WN_BATCH_MAX = int(_os.environ.get("RH_WN_BATCH_MAX", "64"))      # layers per launch (= the table size of the kernel): a pass with more pending layers launches early, on the side stream.
-#                         (16 / 8 per launch -- so that only the last, small layers are left for the join -- measured the same
-#                         step time as one launch at the join: 10.18-10.24 vs 10.16-10.20 ms)
-
-
-def _wn_batch_enabled() -> bool:
-    import os
-    return os.environ.get("RH_WN_BATCH", "1") != "0"
-
-
-# The ordered reductions of the weight gradients' K-slice partials, collected the same way (round 6: 56 launches of 9 - 15 us per
-# v2 step, one behind every split weight-gradient kernel of the side stream): a weight-gradient call of the side stream leaves its
-# partials in a scratch of its own (rh_defer_reduce) and every RH_REDUCE_BATCH layers -- and whenever the gradients are needed: the
-# collected weight-norm launch, a data-parallel bucket, the join -- ONE launch reduces them all, each in the order its own launch
-# would have used (bit-identical; RH_REDUCE_BATCH=0: one launch per layer, at once).
-_RED_PENDING = []       # (ReduceItem, scratch tensor, dw tensor): the tensors are kept alive until the batch has been launched
-_RED_BATCH = 8
-
-
-def _reduce_batch() -> int:
-    """Layers per batched reduction; 0 = one launch per layer.  Default: 8 while a hipGraph is being recorded, 0 in eager steps --
-    there the per-layer scratch allocation and the extra calls cost more host time than the launches they save (measured: the
-    eager v2 step 9.5 -> 11.1 ms with batching, the replayed step unchanged at 232 instead of 281 dispatches).
-    RH_REDUCE_BATCH=n forces n in both modes (read per call: tests)."""
-    import os
-    e = os.environ.get("RH_REDUCE_BATCH")
-    if e is not None:
-        return int(e)
-    return _RED_BATCH if torch.cuda.is_current_stream_capturing() else 0
-
-
-def _flush_reduce_pending(stream_ptr) -> None:
-    items, _RED_PENDING[:] = list(_RED_PENDING), []
-    if not items:
-        return
-    arr = (L.ReduceItem * len(items))()
-    for a, (it, _, _) in zip(arr, items):
-        a.part, a.out, a.n, a.Z = it.part, it.out, it.n, it.Z
-    L.check(L.lib.rh_reduce_partials_batched_f32(arr, len(items), stream_ptr), "reduce_partials_batched")
-
-
-def _flush_wn_pending(stream_ptr) -> None:
-    _flush_reduce_pending(stream_ptr)        # (the weight-norm backward reads the reduced gradients)
-    items, _WN_PENDING[:] = list(_WN_PENDING), []
-    if not items:
-        return
-    arr = (L.WnBwdItem * len(items))()
-    for a, (dw, v, g, norms, dv, dg) in zip(arr, items):
-        a.dw, a.v, a.g, a.norms, a.dv, a.dg = L.ptr(dw), L.ptr(v), L.ptr(g), L.ptr(norms), L.ptr(dv), L.ptr(dg)
-        a.rows = v.shape[0]
-        a.cols = v.numel() // max(v.shape[0], 1)
-    L.check(L.lib.rh_weight_norm_bwd_batched_f32(arr, len(items), stream_ptr), "weight_norm_bwd_batched")
-
-
-def side_stream_for_collective(device):
-    """Data-parallel bucket leaving while the backward pass still runs (rave_amd.ddp.GradReducer._launch): returns the stream
-    the bucket's all-reduce must be ISSUED FROM so that it is ordered behind every gradient written so far -- the
-    weight-gradient side stream, after the collected weight-norm launch of the branch has been enqueued there and after it
-    has been made to wait for the calling (compute) stream -- or None when the branch has nothing in flight.  The compute
-    stream itself is NOT made to wait: the data-gradient chain keeps running while the branch finishes and the collective
-    starts (round 4 joined the branch into the compute stream at every bucket boundary)."""
-    pend = _SIDE_PENDING[0]
-    if pend is None:
-        return None
-    side = pend[1]
-    if _WN_PENDING or _RED_PENDING:
-        with torch.cuda.stream(side):
-            _flush_wn_pending(L.stream())
-    side.wait_stream(torch.cuda.current_stream(device))
-    return side
-
-
-def _graph_task_id() -> int:
-    """Id of the autograd graph task (backward pass) this thread is executing, -1 outside one."""
-    f = getattr(torch._C, "_current_graph_task_id", None)
-    return int(f()) if f is not None else -1
-
-
-def join_side_streams() -> None:
-    """The calling stream waits for everything enqueued on the weight-gradient side stream (after the collected
-    weight-norm backward launches of that branch have been enqueued there)."""
-    pend = _SIDE_PENDING[0]
-    if pend is not None:
-        main, side = pend[0], pend[1]
-        if _WN_PENDING or _RED_PENDING:
-            with torch.cuda.stream(side):
-                _flush_wn_pending(L.stream())
-        main.wait_stream(side)
-        torch.cuda.current_stream().wait_stream(side)
-        _SIDE_PENDING[0] = None
-        _SIDE_HOLD.clear()
-
-
-def abandon_side_streams(rejoin: bool = False) -> None:
-    """Forget the side-stream bookkeeping of a pass that will never be joined (a step whose graph capture was refused midway):
-    no kernel is launched -- the work recorded so far dies with the capture.  rejoin: the calling stream waits for the side
-    streams first, so that a stream capture that forked onto them can be ended."""
-    if rejoin:
-        cur = torch.cuda.current_stream()
-        for st in _SIDE.values():
-            try:
-                cur.wait_stream(st)
-            except Exception:             # noqa: BLE001 -- a side stream that never joined the capture
-                pass
-    _SIDE_PENDING[0] = None
-    _SIDE_HOLD.clear()
-    _WN_PENDING.clear()
-    _RED_PENDING.clear()
-
-
-def _note_use(ctx, *params) -> None:
-    """Forward side of the "exactly one pending use" rule of the side stream: a parameter that enters two nodes of one
-    graph gets its two gradients ADDED by autograd on the compute stream -- which must not happen to a tensor the side
-    stream is still writing.  Every differentiable use bumps a counter on the parameter, every backward takes it down."""
-    ps = [p for p in params if p is not None and p.requires_grad]
-    for p in ps:
-        p._rh_pending = getattr(p, "_rh_pending", 0) + 1
-        if p._rh_pending > 1:
-            p._rh_shared = True          # stays set until every pending use has been taken down
-    ctx.rh_params = ps
-
-
-def _single_use(ctx) -> bool:
-    """Backward side: True iff every parameter of this node has exactly this one pending use and no gradient yet (then the
-    gradient returned here is adopted by autograd without being read).  Always takes the counters down."""
-    ok = True
-    for p in getattr(ctx, "rh_params", ()):
-        n = getattr(p, "_rh_pending", 1)
-        ok = ok and n == 1 and not getattr(p, "_rh_shared", False)
-        # an EXISTING gradient (accumulation over several backward() calls, zero_grad(set_to_none=False), the other
-        # optimizer's parameters in a GAN step) is accumulated into by AccumulateGrad on the COMPUTE stream -- it must not
-        # read a tensor the side stream is still writing (ADVICE r3); likewise the data-parallel hook copies a gradient
-        # into its bucket view on the compute stream when the view was not the one written (slot active but not fresh)
-        if p.grad is not None:
-            ok = False
-        slot = getattr(p, "_rh_grad_slot", None)
-        if slot is not None and len(slot) > 2 and slot[2] and not slot[1]:
-            ok = False
-        p._rh_pending = max(n - 1, 0)
-        if p._rh_pending == 0:
-            p._rh_shared = False
-    return ok
-
-
-class _OnSide:
-    """``with _OnSide(device, tensors...)``: the body is enqueued on the side stream after everything already enqueued on
-    the current stream; ``tensors`` are kept alive for it (caching-allocator stream bookkeeping)."""
-
-    def __init__(self, device, *tensors, allow: bool = True, hold=()):
-        """``hold``: gradient tensors RECEIVED from autograd that the body reads.  The same tensor object may sit in another
-        node's input buffer (``y = conv(x) + other``: AddBackward hands ONE tensor to both branches), and autograd
-        accumulates into a buffered gradient IN PLACE once it is the only holder -- on the compute stream, while the side
-        stream still reads it.  A reference kept until the branch is joined makes that accumulation take the
-        out-of-place form."""
-        self.device = device
-        self.tensors = [t for t in tensors if t is not None]
-        self.hold = [t for t in hold if t is not None]
-        import os
-        self.active = allow and _side_enabled()
-
-    def __enter__(self):
-        if not self.active:
-            return self
-        self.main = torch.cuda.current_stream(self.device)
-        self.side = _side_stream(self.device)
-        self.side.wait_stream(self.main)
-        self.ctx = torch.cuda.stream(self.side)
-        self.ctx.__enter__()
-        return self
-
-    def keep(self, *tensors):
-        self.tensors += [t for t in tensors if t is not None]
-
-    def __exit__(self, *exc):
-        if not self.active:
-            return False
-        self.ctx.__exit__(*exc)
-        for t in self.tensors:
-            t.record_stream(self.side)
-        # The join is queued once per BACKWARD PASS (graph task).  A pass that raised after queueing never ran its callback
-        # and left the pending state behind (ADVICE r4): a pending entry of ANOTHER pass is joined here and now, so that its
-        # collected weight-norm launch still runs and a later pass queues its own join.
-        task = _graph_task_id()
-        pend = _SIDE_PENDING[0]
-        if pend is not None and pend[2] != task:
-            join_side_streams()
-            pend = None
-        # (after the stale join, which clears _SIDE_HOLD: this node's holds must survive until ITS join -- ADVICE r5)
-        if os.environ.get("RH_SIDE_HOLD", "1") != "0":      # (0: the unprotected form, for the test that shows the race)
-            _SIDE_HOLD.extend(self.hold)
-        if pend is None:
-            _SIDE_PENDING[0] = (self.main, self.side, task)
-            try:        # end of this backward pass: the compute stream waits for the branch
-                torch.autograd.Variable._execution_engine.queue_callback(join_side_streams)
-            except RuntimeError:
-                join_side_streams()       # not inside a backward pass (direct call): join at once
-        return False
-
-
-def _arm_wgrad_ranges(dy, x, s, d=None) -> None:
-    """Range slots of both operands for the next weight-gradient call (the f16 weight-gradient kernel converts both)."""
-    if _RANGES and os.environ.get("RH_WGRAD_X6", "1") != "0" and (d is None or L.lib.rh_conv1d_bwd_weight_kernel_family(C.byref(d)) == 1):
-        L.lib.rh_x6_set_ranges(L.ptr(_range_of(dy, s, "wgrad dy")), L.ptr(_range_of(x, s, "wgrad x")), None, None)
+def _wgrad_ranges(dy, x, s, d):
+    """(slot of dy, slot of x) for a weight-gradient call -- the f16 weight-gradient kernel converts both operands --, else
+    (None, None)."""
+    if _RANGES and os.environ.get("RH_WGRAD_X6", "1") != "0" and L.lib.rh_conv1d_bwd_weight_kernel_family(C.byref(d)) == 1:
+        return _range_of(dy, s, "wgrad dy"), _range_of(x, s, "wgrad x")
+    return None, None
 
 
 def _wgrad(d, dy, x, alpha, dw, db, ws, nbytes, s, defer=None):
-    """``defer``: a ReduceItem -- the call may leave the reduction of its K-slice partials to the caller (rh_defer_reduce)."""
-    @_armed_call
+    """``defer``: a ReduceItem -- the call may leave the reduction of its K-slice partials to the caller."""
     def run(o_dw, o_db):
-        _arm_wgrad_ranges(dy, x, s, d)
-        if defer is not None:
-            L.lib.rh_defer_reduce(C.byref(defer))
-        return L.lib.rh_conv1d_bwd_weight_f32(C.byref(d), L.ptr(dy), L.ptr(x), L.ptr(alpha), L.ptr(o_dw), L.ptr(o_db), L.ptr(ws),
-                                              nbytes, s)
+        rdy, rx = _wgrad_ranges(dy, x, s, d)
+        return armed_call(lambda: L.lib.rh_conv1d_bwd_weight_f32(C.byref(d), L.ptr(dy), L.ptr(x), L.ptr(alpha), L.ptr(o_dw), L.ptr(o_db),
+                                                                 L.ptr(ws), nbytes, s), in_a=rdy, in_b=rx, defer=defer)
 
     rc = _launch("conv_wgrad", d, lambda: run(dw, db))
     if rc == 0 and _SHADOW is not None:
         def run_exact(o):
-            L.lib.rh_x6_set_ranges(None, None, None, None)
+            _drop_armed()
             # the exact-f32 kernels plan their own K slices: their scratch is sized under THEIR plan (it used to fit into the
             # bf16x6 path's by accident, while that path cut K into twice as many slices)
             nb2 = L.lib.rh_conv1d_workspace_bytes(C.byref(d))
@@ -842,7 +438,7 @@ def _wn_bwd(dw, v, g, norms, s, slot_v=None, slot_g=None):
 
 def _wgrad_wn(d, dy, x, alpha, dw, db, v, g, norms, ws, nbytes, s, slot_v=None, slot_g=None, side=None):
     """Weight gradient of a weight-normed conv: (dv, dg).  On the side stream (``side.active``) only the weight gradient is
-    launched here; weight norm's backward joins the batch that runs when the branch is joined (_WN_PENDING).  Otherwise ONE C
+    launched here; weight norm's backward joins the batch that runs when the branch is joined (SIDE.wn).  Otherwise ONE C
     call (rh_conv1d_bwd_weight_wn_f32: weight gradient, ordered reduction, weight-norm backward).  The instrumented modes
     (per-launch profile, exact-f32 shadow run) keep the two separate calls they account for."""
     if _PROFILE is not None or _SHADOW is not None:
@@ -858,25 +454,22 @@ def _wgrad_wn(d, dy, x, alpha, dw, db, v, g, norms, ws, nbytes, s, slot_v=None, 
             item = L.ReduceItem()
             L.check(_wgrad(d, dy, x, alpha, dw, db, own, nbytes, s, defer=item), "conv1d_bwd_weight")
             if item.Z > 1:
-                _RED_PENDING.append((item, own, dw))
-                if len(_RED_PENDING) >= nred:
-                    _flush_reduce_pending(s)
+                SIDE.red.append((item, own, dw))
+                if len(SIDE.red) >= nred:
+                    SIDE.flush_reduce(s)
         else:
             L.check(_wgrad(d, dy, x, alpha, dw, db, ws, nbytes, s), "conv1d_bwd_weight")
         # (aliases of dv / dg keep the storage alive until the batch has run; the tensor OBJECTS handed to autograd must have
         # no other holder, or AccumulateGrad clones -- i.e. reads -- them instead of adopting them)
-        _WN_PENDING.append((dw, v, g, norms, dv.detach(), dg.detach()))
-        if len(_WN_PENDING) >= _WN_BATCH_MAX:      # (we are on the side stream here: the batch runs beside the data-gradient chain)
-            _flush_wn_pending(s)
+        SIDE.wn.append((dw, v, g, norms, dv.detach(), dg.detach()))
+        if len(SIDE.wn) >= _WN_BATCH_MAX:      # (we are on the side stream here: the batch runs beside the data-gradient chain)
+            SIDE.flush(s)
         return dv, dg
 
-    @_armed_call
-    def run():
-        _arm_wgrad_ranges(dy, x, s, d)
-        return L.lib.rh_conv1d_bwd_weight_wn_f32(C.byref(d), L.ptr(dy), L.ptr(x), L.ptr(alpha), L.ptr(v), L.ptr(g), L.ptr(norms),
-                                                 L.ptr(dw), L.ptr(dv), L.ptr(dg), L.ptr(db), L.ptr(ws), nbytes, s)
-
-    L.check(run(), "conv1d_bwd_weight_wn")
+    rdy, rx = _wgrad_ranges(dy, x, s, d)
+    L.check(armed_call(lambda: L.lib.rh_conv1d_bwd_weight_wn_f32(C.byref(d), L.ptr(dy), L.ptr(x), L.ptr(alpha), L.ptr(v), L.ptr(g),
+                                                                 L.ptr(norms), L.ptr(dw), L.ptr(dv), L.ptr(dg), L.ptr(db), L.ptr(ws),
+                                                                 nbytes, s), in_a=rdy, in_b=rx), "conv1d_bwd_weight_wn")
     return dv, dg
 
 
@@ -912,8 +505,7 @@ class _ConvFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, wp_b, alpha, v, g, norms, y_act = ctx.saved_tensors
-        if ctx.x_range is not None and getattr(x, "_rh_range", None) is None:
-            x._rh_range = ctx.x_range          # (the saved tensor may come back as a new object)
+        _reattach_range(x, ctx.x_range)
         d = ctx.d
         dref = C.byref(d)
         dy = _chk(dy, "dy")
@@ -1039,10 +631,8 @@ class _ResidualUnitFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, h, wp3b, wp1b, alpha0, alpha2, v3, g3w, n3, v1, g1w, n1 = ctx.saved_tensors
-        if ctx.x_range is not None and getattr(x, "_rh_range", None) is None:
-            x._rh_range = ctx.x_range
-        if ctx.h_range is not None and getattr(h, "_rh_range", None) is None:
-            h._rh_range = ctx.h_range
+        _reattach_range(x, ctx.x_range)
+        _reattach_range(h, ctx.h_range)
         d3, d1 = ctx.d3, ctx.d1
         r3, r1 = C.byref(d3), C.byref(d1)
         dy = _chk(dy, "dy")
@@ -1158,13 +748,8 @@ class _Conv2dFn(torch.autograd.Function):
         y = torch.empty(b, c_out, h_out, w_out, device=dev, dtype=torch.float32)
         rin, rout = _conv2d_ranges(d, 0, x, dev, s, "conv2d x")
 
-        @_armed_call
-        def run_fwd():
-            if rout is not None:
-                L.lib.rh_x6_set_ranges(None, L.ptr(rin), L.ptr(rout), None)
-            return L.lib.rh_conv2d_fwd_f32(dref, L.ptr(x), L.ptr(wp_f), L.ptr(bias), L.ptr(y), s)
-
-        L.check(_launch2("conv2d_fwd", d, run_fwd), "conv2d_fwd")
+        L.check(_launch2("conv2d_fwd", d, lambda: armed_call(
+            lambda: L.lib.rh_conv2d_fwd_f32(dref, L.ptr(x), L.ptr(wp_f), L.ptr(bias), L.ptr(y), s), in_b=rin, out=rout)), "conv2d_fwd")
         _attach_range(y, rout)
         ctx.save_for_backward(x, y if act != ACT_NONE else None, wp_b)
         ctx.d = d
@@ -1189,10 +774,9 @@ class _Conv2dFn(torch.autograd.Function):
                 nb = L.lib.rh_act_bwd_bias_workspace_bytes(d.c_out)
                 wsb = torch.empty(max(nb, 4) // 4, device=dy.device, dtype=torch.float32)
                 rg = _new_range(dy.device) if _ranges_on() else None     # the same sweep leaves max |g| for the f16 kernels
-                if rg is not None:
-                    L.lib.rh_x6_set_ranges(None, None, L.ptr(rg), None)
-                L.check(L.lib.rh_act_bwd_bias_f32(L.ptr(dy), L.ptr(y), d.act, d.act_slope, d.batch, d.c_out, d.h_out * d.w_out,
-                                                  L.ptr(g), L.ptr(db), L.ptr(wsb), nb, s), "act_bwd_bias")
+                L.check(armed_call(lambda: L.lib.rh_act_bwd_bias_f32(L.ptr(dy), L.ptr(y), d.act, d.act_slope, d.batch, d.c_out,
+                                                                     d.h_out * d.w_out, L.ptr(g), L.ptr(db), L.ptr(wsb), nb, s),
+                                   out=rg), "act_bwd_bias")
                 _attach_range(g, rg)
                 need_b = False
             else:
@@ -1205,13 +789,9 @@ class _Conv2dFn(torch.autograd.Function):
             dx = torch.empty_like(x)
             rin, rout = _conv2d_ranges(d, 1, dy, dy.device, s, "conv2d dy") if y is None else (None, None)
 
-            @_armed_call
-            def run_dgrad():
-                if rout is not None:
-                    L.lib.rh_x6_set_ranges(None, L.ptr(rin), L.ptr(rout), None)
-                return L.lib.rh_conv2d_bwd_data_f32(dref, L.ptr(dy), L.ptr(y), L.ptr(wp_b), L.ptr(dx), s)
-
-            L.check(_launch2("conv2d_dgrad", d, run_dgrad), "conv2d_bwd_data")
+            L.check(_launch2("conv2d_dgrad", d, lambda: armed_call(
+                lambda: L.lib.rh_conv2d_bwd_data_f32(dref, L.ptr(dy), L.ptr(y), L.ptr(wp_b), L.ptr(dx), s), in_b=rin, out=rout)),
+                "conv2d_bwd_data")
             _attach_range(dx, rout)
         if ctx.needs_input_grad[1] or need_b:
             dw = torch.empty(ctx.wshape, device=dy.device, dtype=torch.float32)
@@ -1224,14 +804,9 @@ class _Conv2dFn(torch.autograd.Function):
             rdy = _range_of(dy, s, "conv2d wgrad dy") if use_r else None
             rx = _range_of(x, s, "conv2d wgrad x") if use_r else None
 
-            @_armed_call
-            def run_wgrad():
-                if use_r:
-                    L.lib.rh_x6_set_ranges(L.ptr(rdy), L.ptr(rx), None, None)
-                return L.lib.rh_conv2d_bwd_weight_f32(dref, L.ptr(dy), L.ptr(y), L.ptr(x), L.ptr(dw), L.ptr(db) if need_b else None,
-                                                      L.ptr(ws), nbytes, s)
-
-            L.check(_launch2("conv2d_wgrad", d, run_wgrad), "conv2d_bwd_weight")
+            L.check(_launch2("conv2d_wgrad", d, lambda: armed_call(
+                lambda: L.lib.rh_conv2d_bwd_weight_f32(dref, L.ptr(dy), L.ptr(y), L.ptr(x), L.ptr(dw), L.ptr(db) if need_b else None,
+                                                       L.ptr(ws), nbytes, s), in_a=rdy, in_b=rx)), "conv2d_bwd_weight")
         return dx, dw, db, None, None, None, None, None
 
 
@@ -1257,10 +832,8 @@ class _PqmfAnalysisFn(torch.autograd.Function):
         if fold is not None:
             tab, lpad = fold
             ry = _new_range(x.device) if _ranges_on() else None       # the kernel leaves max |y| for the encoder's first conv
-            if ry is not None:
-                L.lib.rh_x6_set_ranges(None, None, L.ptr(ry), None)
-            L.check(L.lib.rh_pqmf_fold_k1_f32(L.ptr(x), L.ptr(tab), rows, t, n_frames, lpad - pad[0], 1.0, L.ptr(y), L.stream()),
-                    "pqmf_fold_k1")
+            L.check(armed_call(lambda: L.lib.rh_pqmf_fold_k1_f32(L.ptr(x), L.ptr(tab), rows, t, n_frames, lpad - pad[0], 1.0, L.ptr(y),
+                                                                 L.stream()), out=ry), "pqmf_fold_k1")
             _attach_range(y, ry)
         else:
             L.check(L.lib.rh_pqmf_analysis_fwd_f32(L.ptr(x), L.ptr(w), rows, t, m, k, pad[0], n_frames, L.ptr(y), L.stream()),
@@ -1609,7 +1182,6 @@ def stft_distance(frames_x: Tensor, frames_y: Tensor, eps: float) -> Tensor:
 
 
 def _stft_one_finalize() -> bool:
-    import os
     return os.environ.get("RH_STFT_ONE_FINALIZE", "1") != "0"
 
 
@@ -1751,7 +1323,6 @@ def _twiddle(n: int, dev) -> Tensor:
 
 
 def _stft_fused_ok(scales, t: int, rows: int) -> bool:
-    import os
     if os.environ.get("RH_STFT_FUSED", "1") == "0":      # 0: framing kernels + rocFFT + spectral kernels (the older path)
         return False
     return all(L.lib.rh_stft_loss_supported(int(n), int(n) // 4, int(t), int(rows)) for n in scales)
@@ -1788,10 +1359,8 @@ class _ReparamFn(torch.autograd.Function):
         nbytes = L.lib.rh_reparam_workspace_bytes()
         ws = torch.empty(nbytes // 4, device=z.device, dtype=torch.float32)
         rz = _new_range(z.device) if _ranges_on() else None           # the kernel leaves max |zs| for the decoder's first conv
-        if rz is not None:
-            L.lib.rh_x6_set_ranges(None, None, L.ptr(rz), None)
-        L.check(L.lib.rh_reparam_fwd_f32(L.ptr(z), L.ptr(eps), b, c, l, L.ptr(zs), L.ptr(kl), L.ptr(ws), nbytes, L.stream()),
-                "reparam_fwd")
+        L.check(armed_call(lambda: L.lib.rh_reparam_fwd_f32(L.ptr(z), L.ptr(eps), b, c, l, L.ptr(zs), L.ptr(kl), L.ptr(ws), nbytes,
+                                                            L.stream()), out=rz), "reparam_fwd")
         _attach_range(zs, rz)
         ctx.save_for_backward(z, eps)
         return zs, kl

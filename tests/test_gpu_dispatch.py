@@ -813,16 +813,16 @@ def test_batched_reduction_of_weight_gradient_partials_is_bit_identical(dev, mon
     tensor, hundreds of slices of a small one -- occur at this width)."""
     from rave_amd import model as M, ops as R
     counts = {}
-    real = R._flush_reduce_pending
+    real = R.SIDE.flush_reduce
 
     def counting(stream_ptr):
-        n = len(R._RED_PENDING)
+        n = len(R.SIDE.red)
         if n:
             counts.setdefault("sizes", []).append(n)
-            counts.setdefault("kinds", set()).update("few" if it.Z <= 16 and it.n >= (1 << 16) else "many" for it, _, _ in R._RED_PENDING)
+            counts.setdefault("kinds", set()).update("few" if it.Z <= 16 and it.n >= (1 << 16) else "many" for it, _, _ in R.SIDE.red)
         return real(stream_ptr)
 
-    monkeypatch.setattr(R, "_flush_reduce_pending", counting)
+    monkeypatch.setattr(R.SIDE, "flush_reduce", counting)
 
     def run(nb):
         counts.clear()
@@ -953,7 +953,7 @@ def test_weight_gradient_through_weight_norm_in_one_launch_equals_the_two_launch
 
 
 def test_collected_weight_norm_backward_equals_one_launch_per_layer(dev):
-    """rave_amd.ops._WN_PENDING: on the weight-gradient side stream the weight-norm backward of every normalization(conv)
+    """rave_amd._side.SideBranch.wn: on the weight-gradient side stream the weight-norm backward of every normalization(conv)
     (rave/blocks.py:15-22) is collected and run as ONE launch when the branch is joined (rh_weight_norm_bwd_batched_f32).
     A chain of weight-normed convs + a fused residual unit, backward through all of them: gradients with the batch on ==
     batch off == side stream off, bit for bit, over repeated trials (a missing join would show as garbage / differing bits);

@@ -1826,7 +1826,7 @@ def test_f16_piece_kernels_keep_f32_accuracy_across_the_dynamic_range_of_a_batch
     xd, wd = x.to(dev).requires_grad_(True), w.to(dev).requires_grad_(True)
     y = R.conv1d(xd, wd, geom=g)
     slot = getattr(y, "_rh_range", None)
-    assert slot is not None and float(slot[0].view(torch.float32).max()) >= float(y.detach().abs().max())
+    assert slot is not None and float(slot.slot.view(torch.float32).max()) >= float(y.detach().abs().max())
     gx, gw = torch.autograd.grad(y, (xd, wd), cot.to(dev))
     x64, w64 = x.double().requires_grad_(True), w.double().requires_grad_(True)
     y64 = F.conv1d(F.leaky_relu(x64, 0.2), w64, padding=3, dilation=3)

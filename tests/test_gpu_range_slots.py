@@ -8,7 +8,7 @@ A. every producer publishes EXACTLY max |output| (each takes the maximum of the 
    the first workgroups, odd offsets), and the kernel family each case exercises asserted;
 B. the consumer at the edges of the scale scheme against fp64 (quiet clips, zero / impulse / huge / tiny / subnormal / non-finite
    tensors);
-C. the slot lifetime rules of rave_amd/ops.py (pools around a recorded step, version counters and views, slots computed on the
+C. the slot lifetime rules of rave_amd/_ranges.py (pools around a recorded step, version counters and views, slots computed on the
    weight-gradient side stream, pool exhaustion in the middle of a step);
 D. the thread-local state rh_x6_set_ranges / rh_defer_reduce / rh_set_kernel_events arm is consumed by a call that fails.
 """
@@ -266,7 +266,7 @@ def test_conv2d_forward_publishes_exactly_max_abs_y(f16, dev, shape, x6):
     ops.range_reset(dev)
     with torch.no_grad():
         y = ops.conv2d(x, w, b, stride=(3, 1), padding=(2, 0))
-    _assert_publishes(y._rh_range[0], y, f"conv2d family {fam}")
+    _assert_publishes(y._rh_range.slot, y, f"conv2d family {fam}")
 
 
 def _conv2d_desc(ops, B, Ci, H, Wd, Co, kh, kw, sh, sw, ph, pw):
@@ -313,13 +313,13 @@ def test_pqmf_analysis_and_reparametrize_publish(f16, dev):
     ops.range_reset(dev)
     with torch.no_grad():
         y = m(x)
-        _assert_publishes(y._rh_range[0], y, "pqmf fold k1")
+        _assert_publishes(y._rh_range.slot, y, "pqmf fold k1")
         gen = torch.Generator().manual_seed(8)
         z = torch.randn(2, 32, 65, generator=gen)
         z[-1, 15, -1] = -90.0                 # a mean far out, negative, last element of the means
         eps = torch.randn(2, 16, 65, generator=gen)
         zs, _ = ops.reparametrize(z.to(dev), eps.to(dev))
-        _assert_publishes(zs._rh_range[0], zs, "reparametrize")
+        _assert_publishes(zs._rh_range.slot, zs, "reparametrize")
         # an edited bank takes the direct-form kernels, which publish nothing: the consumer's rh_amax_f32 pass fills the slot
         m.forward_conv.weight[3, 0, 200] += 1e-2
         assert m._fold(m.forward_conv.weight) is None
@@ -623,7 +623,7 @@ def test_non_finite_inputs_stay_where_fp64_puts_them(f16, dev, bad):
         y1 = ops.conv1d(x0.to(dev), w0.to(dev), geom=g, residual=r.to(dev))
         torch.cuda.synchronize()
         if bad != "nan":
-            assert _smax(y1._rh_range[0]) == float(y1[torch.isfinite(y1)].abs().max())
+            assert _smax(y1._rh_range.slot) == float(y1[torch.isfinite(y1)].abs().max())
         y = ops.conv1d(y1, w.to(dev), geom=g).cpu()
     x1 = F.conv1d(x0.double(), w0.double(), padding=3, dilation=3) + r.double()
     y64 = F.conv1d(x1, w.double(), padding=3, dilation=3)
@@ -721,11 +721,11 @@ def test_a_pool_taken_inside_a_raw_capture_is_not_handed_out_eagerly(f16, dev):
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
         ops.range_reset(dev)
-    owned = ops._RANGE_POOLS[dev][0]
-    assert ops._RANGE_POOLS[dev][4]
+    owned = ops._RANGE_POOLS[dev].pool
+    assert ops._RANGE_POOLS[dev].captured
     slot = ops._new_range(dev)
     assert slot.untyped_storage().data_ptr() != owned.untyped_storage().data_ptr()
-    assert not ops._RANGE_POOLS[dev][4]
+    assert not ops._RANGE_POOLS[dev].captured
     del g
 
 
@@ -746,38 +746,38 @@ def test_version_counters_and_views(f16, dev):
 
     with torch.no_grad():
         y = ops.conv1d(x, w1, geom=g)
-    slot = y._rh_range[0]
+    slot = y._rh_range.slot
     y.mul_(2.0 ** 20)
     out = consume(y)
     assert torch.isfinite(out).all() and rel_l2(out, ref(y)) < 2e-6
     y[0, 0, -1] = 1e6 * 2.0 ** 20
     out = consume(y)
     assert torch.isfinite(out).all() and rel_l2(out, ref(y)) < 2e-6
-    assert _smax(y._rh_range[0]) == float(y.abs().max())
+    assert _smax(y._rh_range.slot) == float(y.abs().max())
     # a view of the whole output: the producer's slot, no pass
     with torch.no_grad():
         y = ops.conv1d(x, w1, geom=g)
-    slot = y._rh_range[0]
+    slot = y._rh_range.slot
     ops.range_miss_log_begin()
     v = y.view(2, 96, 1024)
     consume(v)
     consume(y.reshape(2, 96, 1024))
     assert ops.range_miss_log_end() == []
-    assert v._rh_range[0].data_ptr() == slot.data_ptr()
+    assert v._rh_range.slot.data_ptr() == slot.data_ptr()
     # a partial slice: its own slot, which covers it
     part = y[1:]
     ops.range_miss_log_begin()
     out = consume(part)
     miss = ops.range_miss_log_end()
     assert len(miss) == 1
-    assert part._rh_range[0].data_ptr() != slot.data_ptr()
+    assert part._rh_range.slot.data_ptr() != slot.data_ptr()
     torch.cuda.synchronize()
-    assert _smax(part._rh_range[0]) == float(part.abs().max())
+    assert _smax(part._rh_range.slot) == float(part.abs().max())
     assert rel_l2(out, ref(part)) < 2e-6
 
 
 def test_slot_filled_on_the_side_stream_is_ordered_before_a_compute_stream_reader(f16, dev):
-    """A slot rh_amax_f32 filled on the weight-gradient side stream (ops._arm_wgrad_ranges under _OnSide) must not be read on
+    """A slot rh_amax_f32 filled on the weight-gradient side stream (ops._wgrad_ranges under _OnSide) must not be read on
     the compute stream before that pass has run: a sleep queued on the side stream ahead of the pass makes the race
     deterministic, and the compute-stream consumer must still equal the single-stream result."""
     ops = f16
@@ -806,7 +806,7 @@ def test_pool_exhaustion_in_the_middle_of_a_step_is_bit_identical(f16, dev, monk
     handful of slots the step must land bit for bit where it lands with the default pool, and the replacement must have
     happened while the side stream was in use."""
     ops = f16
-    from rave_amd import model as M
+    from rave_amd import _ranges, model as M
     xb = O.synthetic_batch(2, 1, 32768, seed=65).to(dev)
     eps = torch.randn(2, 128, 16, generator=torch.Generator().manual_seed(4)).to(dev)
 
@@ -820,18 +820,18 @@ def test_pool_exhaustion_in_the_middle_of_a_step_is_bit_identical(f16, dev, monk
 
     p_ref, l_ref = step()
     seen = []
-    orig = ops.range_reset
+    orig = _ranges.range_reset
 
     def spy(device=None, _exhausted=False):
         if _exhausted:
             d_ = device if isinstance(device, torch.device) else torch.device(device)
-            side = ops._SIDE.get(d_.index if d_.index is not None else torch.cuda.current_device())
+            side = ops.SIDE.streams.get(d_.index if d_.index is not None else torch.cuda.current_device())
             # (a weight-gradient branch forked and not yet joined: the side stream is working beside this replacement)
-            seen.append((ops._SIDE_PENDING[0] is not None, side is not None and torch.cuda.current_stream(d_) == side))
+            seen.append((ops.SIDE.pending is not None, side is not None and torch.cuda.current_stream(d_) == side))
         return orig(device, _exhausted)
 
-    monkeypatch.setattr(ops, "_RANGE_SLOTS", 5)
-    monkeypatch.setattr(ops, "range_reset", spy)
+    monkeypatch.setattr(_ranges, "_RANGE_SLOTS", 5)       # (where _new_range looks both up)
+    monkeypatch.setattr(_ranges, "range_reset", spy)
     ops._RANGE_POOLS.clear()
     p, lg = step()
     monkeypatch.undo()
@@ -920,29 +920,114 @@ def test_armed_slots_are_consumed_by_a_failing_call(f16, dev, which):
     assert rel_l2(y.cpu().double(), y64) < 2e-6, which
 
 
-def test_python_side_disarms_when_the_call_raises(f16, dev, monkeypatch):
-    """ops arms the slots of a conv and then calls the library; if that call raises in Python (here: the entry point itself),
-    the armed state is dropped and cannot reach the next call of the thread."""
+def _raise_in_conv1d_fwd(ops, dev, x):
+    xs = x * 2.0 ** -40                 # (armed: an input slot 2^40 too small for x below)
+    ops._range_of(xs, ops.L.stream(), "xs")
+    return lambda: ops.conv1d(xs, _chain_operands(dev, 74)[1], geom=_x6_geom())
+
+
+def _raise_in_act_bwd_bias(ops, dev, x):
+    """conv2d with a bias and an output LeakyReLU, backward: (B, C_out, plane) of test_act_bwd_bias_publishes_g."""
+    gen = torch.Generator().manual_seed(75)
+    x2 = torch.randn(3, 4, 1031, 1, generator=gen).to(dev)
+    w = (torch.randn(37, 4, 3, 1, generator=gen) / 4).to(dev).requires_grad_(True)
+    b = torch.randn(37, generator=gen).to(dev).requires_grad_(True)
+    y = ops.conv2d(x2, w, b, padding=(1, 0), act=ops.ACT_LEAKY, slope=0.2)
+    assert tuple(y.shape) == (3, 37, 1031, 1)
+    return lambda: y.sum().backward()
+
+
+def _raise_in_pqmf_fold_k1(ops, dev, x):
+    from rave_amd import pqmf
+    m = pqmf.CachedPQMF(100, 16).to(dev)
+    assert m._fold(m.forward_conv.weight) is not None         # the folded k1 kernel, not the direct form
+    xw = O.synthetic_batch(2, 1, 8192, seed=4).to(dev)
+    return lambda: m(xw)
+
+
+def _raise_in_reparam_fwd(ops, dev, x):
+    gen = torch.Generator().manual_seed(8)
+    z, eps = torch.randn(2, 32, 65, generator=gen).to(dev), torch.randn(2, 16, 65, generator=gen).to(dev)
+    return lambda: ops.reparametrize(z, eps)
+
+
+def _raise_in_profiled_conv1d_fwd(ops, dev, x):
+    ops._range_of(x, ops.L.stream(), "x")
+    w1 = _chain_operands(dev, 74)[1]
+
+    def call():
+        ops.profile_begin()
+        ops.conv1d(x, w1, geom=_x6_geom())
+    return call
+
+
+class _OnBackwardThread(torch.autograd.Function):
+    """Runs ``fn`` where autograd runs the backward of GPU nodes: a thread of its own, and the armed state is thread-local."""
+
+    @staticmethod
+    def forward(ctx, t, fn):
+        ctx.fn = fn
+        return t.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        ctx.fn()
+        return g, None
+
+
+# (name, entry point made to raise, preparation -> the failing call, in backward): the first is the guarded 1-D forward, the others
+# the sites that armed without a guard before rave_amd/_arming.py (the three publishers of an out-slot, and the kernel events
+# of a profiled launch)
+RAISING_SITES = [
+    ("conv1d forward", "rh_conv1d_fwd_f32", _raise_in_conv1d_fwd, False),
+    ("conv2d backward act_bwd_bias", "rh_act_bwd_bias_f32", _raise_in_act_bwd_bias, True),
+    ("pqmf analysis folded", "rh_pqmf_fold_k1_f32", _raise_in_pqmf_fold_k1, False),
+    ("reparametrize", "rh_reparam_fwd_f32", _raise_in_reparam_fwd, False),
+    ("profiled conv1d forward", "rh_conv1d_fwd_f32", _raise_in_profiled_conv1d_fwd, False),
+]
+
+
+@pytest.mark.parametrize("site", RAISING_SITES, ids=[c[0] for c in RAISING_SITES])
+def test_python_side_disarms_when_the_call_raises(f16, dev, monkeypatch, site):
+    """ops arms the slots (a profiled launch: also the kernel events) of a call and then calls the library; if that call raises
+    in Python (here: the entry point itself), the armed state is dropped and cannot reach the next call of the thread: an
+    unrelated, unarmed 1-D forward stays f32-accurate (an in-slot left armed: 2^40 too small), publishes nothing into the
+    freshly reset pool (an out-slot left armed: the slot the failing call had taken from it) and takes no kernel events."""
     ops = f16
     L = ops.L
+    name, entry, prepare, in_backward = site
     g = _x6_geom()
     x, w1, _ = _chain_operands(dev, 74)
 
     def boom(*a):
         raise RuntimeError("injected")
 
-    ops.range_reset(dev)
-    monkeypatch.setattr(L.lib, "rh_conv1d_fwd_f32", boom)
-    with pytest.raises(RuntimeError, match="injected"), torch.no_grad():
-        ops.conv1d(x * 2.0 ** -40, w1, geom=g)      # (armed: an input slot 2^40 too small for x below)
-    monkeypatch.undo()
     d3 = ops._desc(g, 2, 96, 96, 1024, 1024, 3)
     wp, _, _ = ops._pack(d3, w1, None, False, dev, L.stream())
+    failing = prepare(ops, dev, x)          # (whatever needs a slot has taken it from the pool before this one)
+    ops.range_reset(dev)
+    pool = ops._RANGE_POOLS[dev].pool
+    monkeypatch.setattr(L.lib, entry, boom)
+    with pytest.raises(RuntimeError, match="injected"), torch.set_grad_enabled(in_backward):
+        failing()
+    monkeypatch.undo()
     y = torch.empty_like(x)
-    L.check(L.lib.rh_conv1d_fwd_f32(C.byref(d3), L.ptr(x), L.ptr(wp), None, None, None, L.ptr(y), None, 0, L.stream()), "conv")
+    events_used = []
+
+    def unrelated():
+        L.check(L.lib.rh_conv1d_fwd_f32(C.byref(d3), L.ptr(x), L.ptr(wp), None, None, None, L.ptr(y), None, 0, L.stream()), "conv")
+        events_used.append(L.lib.rh_kernel_events_used())
+
+    if in_backward:         # (the next call of the thread that armed)
+        _OnBackwardThread.apply(torch.zeros(1, device=dev, requires_grad=True), unrelated).sum().backward()
+    else:
+        unrelated()
+    torch.cuda.synchronize()
     ref = F.conv1d(F.leaky_relu(x.double().cpu(), 0.2), w1.double().cpu(), padding=1)
     assert torch.isfinite(y).all()
     assert rel_l2(y.cpu().double(), ref) < 2e-6
+    assert int(pool.abs().max()) == 0
+    assert events_used == [0]
 
 
 def _wgrad_operands(ops, dev):

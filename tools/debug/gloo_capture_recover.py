@@ -34,12 +34,12 @@ def worker(rank, port):
         rc = hip.hipStreamIsCapturing(ctypes.c_void_p(st.cuda_stream), ctypes.byref(v))
         return rc, v.value
     cs = getattr(torch.cuda.graph, "default_capture_stream", None)
-    print(rank, "capture stream", cs, "status", status(cs) if cs is not None else None, "side", [status(s) for s in ops._SIDE.values()], flush=True)
+    print(rank, "capture stream", cs, "status", status(cs) if cs is not None else None, "side", [status(s) for s in ops.SIDE.streams.values()], flush=True)
     if cs is not None:
-        print(rank, "hipStreamEndCapture(capture stream) ->", end_capture(cs), "status", status(cs), "side", [status(s) for s in ops._SIDE.values()], flush=True)
+        print(rank, "hipStreamEndCapture(capture stream) ->", end_capture(cs), "status", status(cs), "side", [status(s) for s in ops.SIDE.streams.values()], flush=True)
         print(rank, "again ->", end_capture(cs), "status", status(cs), flush=True)
     for name, fn in [("is_capturing", lambda: torch.cuda.is_current_stream_capturing()),
-                     ("side capturing", lambda: [s.query() for s in ops._SIDE.values()]),
+                     ("side capturing", lambda: [s.query() for s in ops.SIDE.streams.values()]),
                      ("synchronize", torch.cuda.synchronize),
                      ("zeros", lambda: torch.zeros(1, device=dev)),
                      ("tensor H2D", lambda: torch.tensor([1], device=dev)),
