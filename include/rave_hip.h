@@ -507,6 +507,24 @@ int rh_stft_loss_bwd_f32(const float* x, const float* y, const float* window, co
                          int32_t t_len, int32_t n_fft, float eps, const float* sums, const float* grad_out, float* dx,
                          float* dy, int32_t accumulate, rh_stream_t stream);
 
+/* The mel-spectrogram encoder input of RAVE.input_mode = "mel" (rave/model.py:238-242: `spectrogram(x)[..., :-1]`, log1p,
+ * reshape; spectrogram = torchaudio.transforms.MelSpectrogram as configs/hybrid.gin binds it) in one launch, forward only
+ * (nothing trainable is upstream of the audio).  x (rows, t_len) f32; window (n_fft: the module's `spectrogram.window`);
+ * twiddle as for rh_stft_loss_fwd_f32 (8-byte aligned); fb (n_fft / 2 + 1, n_mels: the module's `mel_scale.fb`); bins
+ * (n_mels, 2) int32: filter m is zero outside the bins [bins[2m], bins[2m+1]) (clamped to [0, n_fft / 2 + 1] by the kernel).
+ *   y[row][m][f] = g(sum_k fb[k][m] * |rfft(window * frame_f)_k|^2 * scale),   g = log1p (log1p != 0) or the identity,
+ * frame_f = the n_fft samples centred on f * hop of the reflect-padded row; scale = 1 / sum(window^2) for `normalized=True`,
+ * else 1.  n_frames = t_len / hop (the reference drops the last frame) or t_len / hop + 1 (all of torchaudio's frames).
+ * y is (rows, n_mels, n_frames): with rows = B * n_channels a reshape gives the encoder's (B, n_channels * n_mels, frames).
+ * Sizes (rh_mel_supported answers 1 / 0): n_fft in {128, 256, 512, 1024, 2048}, 1 <= hop <= n_fft, 1 <= n_mels <= 128,
+ * t_len > n_fft / 2, t_len >= hop, 0 < rows < 65536 -- anything else is RH_ERR_UNSUPPORTED; null pointers, a misaligned
+ * twiddle table, another n_frames and a scale that is not positive and finite are RH_ERR_INVALID; nothing is enqueued in
+ * any of these cases.  Every sum has one fixed order (no atomics): results are bit-identical from run to run. */
+int rh_mel_supported(int32_t n_fft, int32_t hop, int32_t n_mels, int32_t t_len, int64_t rows);
+int rh_mel_fwd_f32(const float* x, const float* window, const float* twiddle, const float* fb, const int32_t* bins,
+                   int64_t rows, int32_t t_len, int32_t n_fft, int32_t hop, int32_t n_mels, int32_t n_frames, float scale,
+                   int32_t log1p, float* y, rh_stream_t stream);
+
 /* Measurement hook (bench.py's roofline leg; not part of the reference interface): arm a pair of HIP events (hipEvent_t,
  * created by the caller with timing enabled) for the calling thread's NEXT main kernel launch -- the convolution /
  * weight-gradient kernel of rh_conv1d_fwd_f32 / _bwd_data_f32 / _bwd_weight_f32 / rh_residual_unit_fwd_f32, not its split-K

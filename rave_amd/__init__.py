@@ -7,3 +7,12 @@ layouts; all arithmetic runs in hand-written HIP kernels behind the C ABI of
 ``include/rave_hip.h`` (``rave_amd/librave_hip.so``).
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # rave_amd.MelSpectrogram (torchaudio.transforms.MelSpectrogram's stand-in, rave_amd/mel.py), resolved on first use: importing
+    # the package itself stays free of torch (rave_amd.build runs before anything else exists)
+    if name == "MelSpectrogram":
+        from .mel import MelSpectrogram
+        return MelSpectrogram
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,0 +1,196 @@
+// The in-LDS complex FFT shared by stft_loss.hip and mel.hip (N = 128 ... 2048; Stockham autosort, radix 8 + one radix 2 / 4
+// pass, N / 8 threads per transform, 256 / (N / 8) transforms per workgroup side by side), the reflect index of a centred
+// frame and the power-of-two equaliser of a frame pair.  Included INSIDE the including file's anonymous namespace, after
+// common.hpp; see the header of stft_loss.hip for the scheme.
+
+typedef float c32 __attribute__((ext_vector_type(2)));       // complex as a packed pair: adds / twiddle products are v_pk_* ops
+
+__device__ __forceinline__ c32 mk(float a, float b) { c32 r; r.x = a; r.y = b; return r; }
+__device__ __forceinline__ c32 cmul(c32 a, c32 w) {
+    c32 r = a.xx * w;
+    return __builtin_elementwise_fma(a.yy, mk(-w.y, w.x), r);
+}
+__device__ __forceinline__ c32 mul_mi(c32 a) { return mk(a.y, -a.x); }          // a * (-i)
+
+// forward DFTs (e^{-i}) of 2 / 4 / 8 points in natural order, in place on v[0], v[S], v[2S] ...
+template <int S>
+__device__ __forceinline__ void dft2(c32* v) {
+    const c32 a = v[0], b = v[S];
+    v[0] = a + b;
+    v[S] = a - b;
+}
+template <int S>
+__device__ __forceinline__ void dft4(c32* v) {
+    const c32 b0 = v[0] + v[2 * S], b1 = v[0] - v[2 * S];
+    const c32 b2 = v[S] + v[3 * S], b3 = mul_mi(v[S] - v[3 * S]);
+    v[0] = b0 + b2;
+    v[S] = b1 + b3;
+    v[2 * S] = b0 - b2;
+    v[3 * S] = b1 - b3;
+}
+__device__ __forceinline__ void dft8(c32* v) {
+    dft4<2>(v);          // even samples -> E_k at v[2k]
+    dft4<2>(v + 1);      // odd samples  -> O_k at v[2k+1]
+    constexpr float kR = 0.70710678118654752440f;
+    const c32 e0 = v[0], e1 = v[2], e2 = v[4], e3 = v[6];
+    const c32 o0 = v[1];
+    const c32 o1 = mk(v[3].x + v[3].y, v[3].y - v[3].x) * kR;         // * (1 - i) / sqrt 2
+    const c32 o2 = mul_mi(v[5]);
+    const c32 o3 = mk(v[7].y - v[7].x, -(v[7].x + v[7].y)) * kR;      // * (-1 - i) / sqrt 2
+    v[0] = e0 + o0; v[4] = e0 - o0;
+    v[1] = e1 + o1; v[5] = e1 - o1;
+    v[2] = e2 + o2; v[6] = e2 - o2;
+    v[3] = e3 + o3; v[7] = e3 - o3;
+}
+template <int R>
+__device__ __forceinline__ void dft(c32* v) {
+    if (R == 8) dft8(v);
+    else if (R == 4) dft4<1>(v);
+    else dft2<1>(v);
+}
+
+__device__ __forceinline__ int zpad(int i) { return i + (i >> 3); }
+
+template <int N>
+struct Fft {
+    static constexpr int TPF = N / 8;                       // threads per transform
+    static constexpr int G = 256 / TPF;                     // transforms per workgroup
+    static constexpr int ZP = N + N / 8;                    // padded LDS image
+    static constexpr int P8 = N >= 512 ? 3 : 2;             // radix-8 passes
+    static constexpr int LAST = N / (P8 == 3 ? 512 : 64);   // then one pass of radix 2 / 4 (1: none)
+    static constexpr int RF = LAST > 1 ? LAST : 8;          // radix of the final pass
+    static constexpr int NSF = N / RF;
+    static constexpr int NSL = LAST > 1 ? (P8 == 3 ? 512 : 64) : (P8 == 3 ? 64 : 8);    // NS of the final pass
+    static constexpr bool MID2 = P8 == 3 && LAST > 1;       // a second middle pass (NS = 64)
+    static constexpr int NTF = (RF - 1) * (8 / RF);
+
+    // A transform's threads sit in ONE wave when TPF <= 64: LDS traffic of a wave is executed in order, no barrier needed
+    static __device__ __forceinline__ void sync() {
+        if (TPF > 64) __syncthreads();
+        else __builtin_amdgcn_wave_barrier();
+    }
+
+    // every twiddle a thread ever needs depends on its index alone: fetched once, kept in registers across the frames
+    struct Tw {
+        c32 a[7];            // pass NS = 8
+        c32 b[MID2 ? 7 : 1]; // pass NS = 64 (1024 / 2048 only)
+        c32 f[NTF];          // final pass
+        __device__ __forceinline__ void init(int t, const c32* __restrict__ tw) {
+#pragma unroll
+            for (int r = 1; r < 8; ++r) a[r - 1] = tw[r * (t & 7) * (N / 64)];
+            if (MID2) {
+#pragma unroll
+                for (int r = 1; r < 8; ++r) b[r - 1] = tw[r * (t & 63) * (N / 512)];
+            }
+#pragma unroll
+            for (int u = 0; u < 8 / RF; ++u) {
+                const int k = (t + u * TPF) & (NSL - 1);
+#pragma unroll
+                for (int r = 1; r < RF; ++r) f[u * (RF - 1) + r - 1] = tw[r * k * (N / (NSL * RF))];
+            }
+        }
+    };
+
+    // one Stockham pass: butterfly j = t + u TPF (u < 8 / R) takes in[j + r N/R], twiddles by e^{-2 pi i r k / (NS R)},
+    // k = j mod NS, and its output r goes to (j - k) R + k + r NS.  With the padded index i + i/8 every address is a
+    // per-thread base plus a compile-time constant (n/8 and NS >= 8 are multiples of 8): immediate offsets, no index math
+    // per access.
+    template <int R>
+    static __device__ __forceinline__ void load(c32 (&v)[8], const c32* z, int t, const c32* w) {
+        const c32* zt = z + zpad(t);
+#pragma unroll
+        for (int u = 0; u < 8 / R; ++u) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                c32 a = zt[(u * TPF + r * (N / R)) / 8 * 9];
+                if (r > 0) a = cmul(a, w[u * (R - 1) + r - 1]);
+                v[u * R + r] = a;
+            }
+        }
+    }
+    template <int R>
+    static __device__ __forceinline__ void bfly(c32 (&v)[8]) {
+#pragma unroll
+        for (int u = 0; u < 8 / R; ++u) dft<R>(&v[u * R]);
+    }
+    // radix-8 passes only (R = 8, one butterfly per thread: j = t)
+    template <int NS>
+    static __device__ __forceinline__ void store8(const c32 (&v)[8], c32* z, int t) {
+        const int k = t & (NS - 1);
+        // NS = 1: 9 t + r;  NS = 8: 9 (t - k) + k + 9 r;  NS = 64: 9 (t - k) + k + k / 8 + 72 r
+        c32* zt = z + 9 * (t - k) + k + (k >> 3);
+#pragma unroll
+        for (int r = 0; r < 8; ++r) zt[NS == 1 ? r : r * NS / 8 * 9] = v[r];
+    }
+    template <int NS>
+    static __device__ __forceinline__ void pass8(c32 (&v)[8], c32* z, int t, const c32* w) {
+        load<8>(v, z, t, w);
+        bfly<8>(v);
+        sync();
+        store8<NS>(v, z, t);
+        sync();
+    }
+    // first pass with the 8 inputs v[r] = in[t + r TPF] already in registers; leaves everything but the final pass done
+    // and returns with the final pass's butterflies in v: output r of butterfly u is sample (t + u TPF) + r NSF.
+    // Every thread of the workgroup must call it (barriers); the caller guarantees nobody still reads z.
+    static __device__ __forceinline__ void run(c32 (&v)[8], c32* z, int t, const Tw& tw) {
+        bfly<8>(v);
+        store8<1>(v, z, t);
+        sync();
+        if (P8 == 3 || LAST > 1) pass8<8>(v, z, t, tw.a);
+        if (MID2) pass8<64>(v, z, t, tw.b);
+        load<RF>(v, z, t, tw.f);
+        bfly<RF>(v);
+        sync();                                             // all reads of z done: the caller may overwrite it
+    }
+    static __device__ __forceinline__ int out_index(int t, int u, int r) { return t + u * TPF + r * NSF; }
+    // natural-order spectrum into z (barrier at the end)
+    static __device__ __forceinline__ void store_natural(const c32 (&v)[8], c32* z, int t) {
+        c32* zt = z + zpad(t);
+#pragma unroll
+        for (int u = 0; u < 8 / RF; ++u)
+#pragma unroll
+            for (int r = 0; r < RF; ++r) zt[(u * TPF + r * NSF) / 8 * 9] = v[u * RF + r];
+        sync();
+    }
+};
+
+__device__ __forceinline__ int reflect_at(int p, int t) { return p < 0 ? -p : (p >= t ? 2 * (t - 1) - p : p); }
+
+// Equaliser of a frame pair: s = 2^(e_x - e_y) from the largest |x| and |y| of the frame (all N samples: the TPF threads of
+// the transform; across waves through `fmx`, one slot per wave -- the barriers inside the transform that follows separate this
+// read from the next frame's write), 1 when either frame is all zero.  Every thread of the workgroup must call it.
+template <int TPF>
+__device__ __forceinline__ void frame_scale(const c32 (&vn)[8], c32* fmx, float& s, float& inv_s, int on) {
+    float mx = 0.f, my = 0.f;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        mx = fmaxf(mx, fabsf(vn[r].x));
+        my = fmaxf(my, fabsf(vn[r].y));
+    }
+    constexpr int W = TPF < 64 ? TPF : 64;
+#pragma unroll
+    for (int o = W / 2; o >= 1; o >>= 1) {
+        mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+        my = fmaxf(my, __shfl_xor(my, o, 64));
+    }
+    if (TPF > 64) {
+        const int wave = threadIdx.x >> 6;
+        if ((threadIdx.x & 63) == 0) fmx[wave] = mk(mx, my);
+        __syncthreads();
+        const int w0 = (threadIdx.x / TPF) * (TPF / 64);
+        mx = my = 0.f;
+#pragma unroll
+        for (int i = 0; i < TPF / 64; ++i) {
+            const c32 q = fmx[w0 + i];
+            mx = fmaxf(mx, q.x);
+            my = fmaxf(my, q.y);
+        }
+    }
+    int d = (mx > 0.f && my > 0.f) ? (int)(__float_as_uint(mx) >> 23) - (int)(__float_as_uint(my) >> 23) : 0;
+    d = d < -100 ? -100 : (d > 100 ? 100 : d);
+    if (!on) d = 0;
+    if (TPF >= 64) d = __builtin_amdgcn_readfirstlane(d);      // a whole wave works on one transform: the scale lives in an SGPR
+    s = __uint_as_float((unsigned)(127 + d) << 23);
+    inv_s = __uint_as_float((unsigned)(127 - d) << 23);
+}

@@ -61,9 +61,22 @@ class RAVE(nn.Module):
                  audio_distance: Callable[[], nn.Module], multiband_audio_distance: Callable[[], nn.Module],
                  n_bands: int = 16, weights: Optional[Dict[str, float]] = None,
                  pqmf: Optional[Callable[[], nn.Module]] = None, update_discriminator_every: int = 2,
-                 n_channels: int = 1):
+                 n_channels: int = 1, spectrogram: Optional[nn.Module] = None, input_mode: str = "pqmf",
+                 output_mode: str = "pqmf"):
         super().__init__()
+        # rave/model.py:168-175.  "mel" (configs/hybrid.gin, v2_with_augs.gin) feeds the encoder log1p of `spectrogram`; the
+        # raw-waveform modes are not built
+        if input_mode not in ("pqmf", "mel", "raw") or output_mode not in ("pqmf", "raw"):
+            raise ValueError(f"RAVE: input_mode {input_mode!r} / output_mode {output_mode!r}")
+        for which, mode in (("input_mode", input_mode), ("output_mode", output_mode)):
+            if mode == "raw":
+                raise NotImplementedError(f'rave_amd RAVE: {which} = "raw" is not built (the raw-waveform configs)')
+        if input_mode == "mel" and spectrogram is None:
+            raise ValueError('RAVE: input_mode = "mel" needs `spectrogram`')
         self.pqmf = pqmf(n_channels=n_channels)
+        self.spectrogram = spectrogram   # (None is a plain attribute: the default model keeps its state_dict keys)
+        self.input_mode = input_mode
+        self.output_mode = output_mode
         self.encoder = encoder(n_channels=n_channels)
         self.decoder = decoder(n_channels=n_channels)
         self.discriminator = discriminator(n_channels=n_channels)
@@ -172,11 +185,26 @@ class RAVE(nn.Module):
         return self._opts
 
     # ---- rave/model.py:244-270
+    def _mel_encode(self, x: torch.Tensor):
+        """rave/model.py:238-242: ``log1p(spectrogram(x)[..., :-1])`` as (*batch, n_channels * n_mels, frames).  The drop-in
+        module does all of it in one HIP launch (rave_amd.mel.MelSpectrogram.log_mel); any other callable runs the reference's
+        statements.  Never requires grad: nothing trainable is upstream of the audio."""
+        batch_size = x.shape[:-2]
+        with torch.no_grad():
+            if hasattr(self.spectrogram, "log_mel"):
+                m = self.spectrogram.log_mel(x)
+            else:
+                m = torch.log1p(self.spectrogram(x)[..., :-1])
+        return m.reshape(*batch_size, -1, m.shape[-1])
+
     def encode(self, x, return_mb: bool = False):
-        x_enc = _pqmf_encode(self.pqmf, x)
-        z = self.encoder(x_enc)
+        """In mel mode ``return_mb`` gives the PQMF of the RAW audio: the reference (rave/model.py:255-256) hands the mel tensor
+        to the PQMF there, which its own training_step cannot run with; the raw-mode branch of the
+        same function shows the intent."""
+        x_mb = _pqmf_encode(self.pqmf, x) if (self.input_mode == "pqmf" or return_mb) else None
+        z = self.encoder(x_mb if self.input_mode == "pqmf" else self._mel_encode(x))
         if return_mb:
-            return z, x_enc
+            return z, x_mb
         return z
 
     def decode(self, z):
@@ -273,7 +301,8 @@ class RAVE(nn.Module):
                 self._rf_host = tuple(int(v) for v in self.receptive_field.tolist())
             rf = getattr(self, "_rf_host", (0, 0))
         x_mb_loss = valid_signal_crop(x_multiband, rf[0], rf[1]) if rf[0] + rf[1] else x_multiband
-        z = self.encoder(x_multiband)
+        # mel mode: only the encoder sees the mel tensor, the multiband distance keeps the PQMF of the raw audio (see encode)
+        z = self.encoder(x_multiband if self.input_mode == "pqmf" else self._mel_encode(x_raw))
         z, reg = self.encoder.reparametrize(z, eps)[:2]
 
         y = self.decoder(z)
@@ -705,33 +734,53 @@ def build_v2(n_channels: int = 1, capacity: int = 96, ratios=(4, 4, 4, 2), laten
              noise: bool = False, update_discriminator_every: int = 4, discriminator_kind: str = "v2",
              encoder_kind: str = "variational", noise_augmentation: int = 0, num_quantizers: int = 16,
              codebook_size: int = 1024, log_epsilon: float = 1e-7, num_skipped_features: int = 1,
-             spectral_capacity: int = 32, gru_layers: int = 0) -> RAVE:
+             spectral_capacity: int = 32, gru_layers: int = 0, mel_input: bool = False, n_fft: int = 2048,
+             hop_length: int = 256, n_mels: int = 128, encoder_ratios=(2, 2, 2), encoder_dilations=(1,)) -> RAVE:
     """configs/v1.gin + configs/v2.gin transcribed (cf. oracle/ref_models.py for the citations).
     ``snake`` / ``adain`` add the generator-side overlays of configs/v3.gin (snake.gin: every activation
     -> blocks.Snake; adain.gin: AdaptiveInstanceNormalization before every unit); ``causal`` =
     configs/causal.gin.  ``discriminator_kind``: "v2" (MPD + MSD, v2.gin:53-75), "descript"
     (descript_discriminator.gin), "spectral" (spectral_discriminator.gin: MSD + Encodec STFT nets).
     ``encoder_kind``: "variational" or "discrete" (discrete.gin: EncoderV2(n_out=1) + RVQ + noise channels).
-    ``gru_layers`` > 0 puts blocks.GRU in front of the decoder (the generator half of configs/hybrid.gin:33-38; its mel
-    encoder input is not provided)."""
+    ``gru_layers`` > 0 puts blocks.GRU in front of the decoder (the generator half of configs/hybrid.gin:33-38).
+    ``mel_input`` is the encoder half (hybrid.gin:11-31, 40-42): RAVE.input_mode = "mel" with rave_amd.MelSpectrogram
+    (``n_fft``, ``hop_length``, ``n_mels``, normalized) and EncoderV2(data_size = n_mels * n_channels as the reference's
+    encoder computes it, ``encoder_ratios``, ``encoder_dilations``); the decoder keeps ``ratios`` / ``dilations``."""
+    ratios = list(ratios)
+    spectrogram = None
+    if mel_input:
+        enc_rate, dec_rate = int(hop_length), int(n_band)
+        for r in encoder_ratios:
+            enc_rate *= int(r)
+        for r in ratios:
+            dec_rate *= int(r)
+        if enc_rate != dec_rate:
+            raise ValueError(f"build_v2(mel_input=True): the encoder makes one latent frame per hop_length x prod(encoder_ratios) = "
+                             f"{enc_rate} samples, the decoder turns one into n_band x prod(ratios) = {dec_rate}: they must agree")
+        from .mel import MelSpectrogram
+        spectrogram = MelSpectrogram(sample_rate=sampling_rate, n_fft=n_fft, win_length=n_fft, hop_length=hop_length,
+                                     normalized=True, n_mels=n_mels)
     cc.set_default_padding_mode("causal" if causal else "centered")
     blocks.set_normalization_mode("weight_norm")
     dil = dilations or V2_DILATIONS
-    ratios = list(ratios)
     extra = {}
     blocks.set_dilated_unit_activation(blocks.Snake if snake else None)
     if snake:
         extra["activation"] = blocks.Snake
     if adain:
         extra["adain"] = blocks.AdaptiveInstanceNormalization
+    # the encoder's own geometry: the PQMF bands at the decoder's ratios, or (hybrid.gin:17-20) the mel channels at its own
+    enc_geom = dict(data_size=n_band, ratios=ratios, dilations=dil)
+    if mel_input:
+        enc_geom = dict(data_size=int(n_mels), ratios=[int(r) for r in encoder_ratios], dilations=[int(d) for d in encoder_dilations])
     if encoder_kind == "variational":
         enc = partial(blocks.VariationalEncoder,
-                      encoder=partial(blocks.EncoderV2, data_size=n_band, capacity=capacity, ratios=ratios,
-                                      latent_size=latent_size, n_out=2, kernel_size=3, dilations=dil, **extra))
+                      encoder=partial(blocks.EncoderV2, capacity=capacity, latent_size=latent_size, n_out=2, kernel_size=3,
+                                      **enc_geom, **extra))
     elif encoder_kind == "discrete":   # configs/discrete.gin:24-40
         enc = partial(blocks.DiscreteEncoder,
-                      encoder_cls=partial(blocks.EncoderV2, data_size=n_band, capacity=capacity, ratios=ratios,
-                                          latent_size=latent_size, n_out=1, kernel_size=3, dilations=dil, **extra),
+                      encoder_cls=partial(blocks.EncoderV2, capacity=capacity, latent_size=latent_size, n_out=1, kernel_size=3,
+                                          **enc_geom, **extra),
                       vq_cls=partial(quantization.ResidualVectorQuantization, num_quantizers=num_quantizers,
                                      dim=latent_size, codebook_size=codebook_size),
                       num_quantizers=num_quantizers, noise_augmentation=noise_augmentation)
@@ -773,7 +822,8 @@ def build_v2(n_channels: int = 1, capacity: int = 96, ratios=(4, 4, 4, 2), laten
                  feature_matching_fun=partial(losses.mean_difference, norm="L1", relative=True),
                  num_skipped_features=num_skipped_features, audio_distance=dist, multiband_audio_distance=dist,
                  weights={"feature_matching": 20}, update_discriminator_every=update_discriminator_every,
-                 n_channels=n_channels, n_bands=n_band)
+                 n_channels=n_channels, n_bands=n_band, spectrogram=spectrogram,
+                 input_mode="mel" if mel_input else "pqmf")
     cc.set_default_padding_mode("centered")
     blocks.set_dilated_unit_activation(None)
     return model

@@ -1342,6 +1342,35 @@ def multiscale_stft_distance(x: Tensor, y: Tensor, windows, scales, eps: float) 
     return _MultiScaleStftDistanceFn.apply(x, y, float(eps), tuple(int(s) for s in scales), *windows)
 
 
+# --------------------------------------------------------------------------- mel-spectrogram encoder input
+def mel_supported(n_fft: int, hop: int, n_mels: int, t: int, rows: int) -> bool:
+    return L.lib.rh_mel_supported(int(n_fft), int(hop), int(n_mels), int(t), int(rows)) == 1
+
+
+def mel_spectrogram(x: Tensor, window: Tensor, fb: Tensor, bins: Tensor, hop: int, scale: float, log1p: bool,
+                    drop_last: bool) -> Tensor:
+    """(..., T) -> (..., n_mels, T // hop [+ 1]) on rh_mel_fwd_f32 (rave/model.py:238-242 with ``log1p`` and ``drop_last``).
+    Forward only: the result does not require grad (nothing trainable is upstream of the audio), so the convolution that
+    consumes it launches no data gradient.  It carries no range slot: the first x6 convolution that reads it takes the
+    rh_amax_f32 pass (_range_of), like every tensor no convolution produced."""
+    x = _chk(x.detach(), "x")
+    window, fb = _chk(window, "window"), _chk(fb, "fb")
+    if bins.dtype != torch.int32 or not bins.is_cuda or not bins.is_contiguous():
+        raise RuntimeError("rave_amd mel_spectrogram: bins must be a contiguous int32 GPU tensor")
+    n_fft, n_mels, t = window.numel(), fb.shape[1], x.shape[-1]
+    rows = x.numel() // max(t, 1)
+    if tuple(fb.shape) != (n_fft // 2 + 1, n_mels) or tuple(bins.shape) != (n_mels, 2):
+        raise RuntimeError(f"rave_amd mel_spectrogram: fb {tuple(fb.shape)} / bins {tuple(bins.shape)} do not fit n_fft {n_fft}")
+    if not mel_supported(n_fft, hop, n_mels, t, rows):
+        raise NotImplementedError(f"rave_amd mel_spectrogram: (n_fft {n_fft}, hop {hop}, n_mels {n_mels}, T {t}, rows {rows}) "
+                                  "is not built (include/rave_hip.h: rh_mel_supported)")
+    n_frames = t // hop + (0 if drop_last else 1)
+    y = torch.empty(x.shape[:-1] + (n_mels, n_frames), device=x.device, dtype=torch.float32)
+    L.check(L.lib.rh_mel_fwd_f32(L.ptr(x), L.ptr(window), L.ptr(_twiddle(n_fft, x.device)), L.ptr(fb), L.ptr(bins), rows, t, n_fft,
+                                 int(hop), n_mels, n_frames, float(scale), int(bool(log1p)), L.ptr(y), L.stream()), "mel_fwd")
+    return y
+
+
 # --------------------------------------------------------------------------- reparametrisation + KL
 class _ReparamFn(torch.autograd.Function):
     """VariationalEncoder.reparametrize (rave/blocks.py:727-745) on rh_reparam_{fwd,bwd}_f32: (zs, kl) from z = [mean | scale]
