@@ -650,6 +650,23 @@ int rh_reparam_fwd_f32(const float* z, const float* eps, int32_t batch, int32_t 
 int rh_reparam_bwd_f32(const float* z, const float* eps, const float* dzs, const float* dkl, int32_t batch, int32_t c,
                        int32_t l, float* dz, rh_stream_t stream);
 
+/* Latent-space analysis at the end of validation (rave/model.py:463-481: `z = cat(z, 0)`, `rearrange(z, "b c t -> (b t) c")`,
+ * `z.mean(0)`, `PCA(...).fit(z)`): the first and second moments of the posterior mean, accumulated one validation batch per
+ * call.  `mean` is f32 (batch, channels, t_len) as validation_step returns it, time innermost, any 4-byte aligned address:
+ * the rows of the statistics are the (b, t) pairs, the rearrange is addressing.  `acc` is the caller's accumulator of
+ * 1 + channels + channels^2 doubles (8-byte aligned; zero it before the first call):
+ *   acc[0] += batch * t_len,   acc[1 + i] += sum z[b,i,t],   acc[1 + channels + i * channels + j] += sum z[b,i,t] * z[b,j,t].
+ * f64 arithmetic: the products of f32 values are exact, only the additions round.  No atomics; the split of the rows over
+ * workgroups depends on (batch, t_len) only, the per-workgroup partials go through `workspace`
+ * (rh_latent_moments_workspace_bytes, 8-byte aligned, contents irrelevant before and after) and are added in a fixed order:
+ * the same sequence of calls gives bit-identical accumulators.  Calls on one accumulator must be stream-ordered.
+ * 1 <= channels <= 128 (rh_latent_moments_supported answers 1 / 0); more channels, non-positive sizes, null or misaligned
+ * pointers are RH_ERR_INVALID and enqueue nothing. */
+int rh_latent_moments_supported(int32_t channels);
+int rh_latent_moments_workspace_bytes(int32_t batch, int32_t channels, int32_t t_len, int64_t* bytes);
+int rh_latent_moments_acc_f64(const float* mean, int32_t batch, int32_t channels, int32_t t_len, double* acc, void* workspace,
+                              rh_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

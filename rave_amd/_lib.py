@@ -159,6 +159,9 @@ def _load() -> C.CDLL:
         "rh_gru_workspace_bytes": ([I32, I32, I32, I32, I32, C.POINTER(I64)], C.c_int),
         "rh_gru_fwd_f32": ([P, C.POINTER(GruItem), I32, I32, I32, I32, I32, P, P, I64, P], C.c_int),
         "rh_gru_bwd_f32": ([P, P, C.POINTER(GruItem), I32, I32, I32, I32, P, P, I64, P], C.c_int),
+        "rh_latent_moments_supported": ([I32], C.c_int),
+        "rh_latent_moments_workspace_bytes": ([I32, I32, I32, C.POINTER(I64)], C.c_int),
+        "rh_latent_moments_acc_f64": ([P, I32, I32, I32, P, P, P], C.c_int),
         "rh_x6_uses_ranges": ([], C.c_int),
         "rh_x6_range_words": ([], C.c_int),
         "rh_x6_set_ranges": ([P, P, P, P], C.c_int),

@@ -62,7 +62,7 @@ class RAVE(nn.Module):
                  n_bands: int = 16, weights: Optional[Dict[str, float]] = None,
                  pqmf: Optional[Callable[[], nn.Module]] = None, update_discriminator_every: int = 2,
                  n_channels: int = 1, spectrogram: Optional[nn.Module] = None, input_mode: str = "pqmf",
-                 output_mode: str = "pqmf"):
+                 output_mode: str = "pqmf", latent_analysis: bool = False):
         super().__init__()
         # rave/model.py:168-175.  "mel" (configs/hybrid.gin, v2_with_augs.gin) feeds the encoder log1p of `spectrogram`; the
         # raw-waveform modes are not built
@@ -97,6 +97,13 @@ class RAVE(nn.Module):
         self.beta_factor = 1.
         self._beta_dev = None          # 0-d device copy of beta_factor read by the recorded (hipGraph) step
         self.register_buffer("receptive_field", torch.tensor([0, 0]).long())
+        # rave/model.py:196-198: the export-time analysis buffers validation_epoch_end fills.  Opt-in: without the keyword the
+        # module tree and state_dict are what they were before the analysis existed
+        self.latent_analysis = bool(latent_analysis)
+        if self.latent_analysis:
+            self.register_buffer("latent_pca", torch.eye(latent_size))
+            self.register_buffer("latent_mean", torch.zeros(latent_size))
+            self.register_buffer("fidelity", torch.zeros(latent_size))
         self.logged: Dict[str, torch.Tensor] = {}
         self._opts = None
         self._gen_sched = None
@@ -462,6 +469,84 @@ class RAVE(nn.Module):
         self.release_weights()
         return torch.cat([x, y], -1), mean
 
+    # ---- rave/core.py:180-217
+    def measure_receptive_field(self):
+        """``rave.core.get_rave_receptive_field``: the input gradient of one output sample of the eval-mode model, the signal
+        length doubled from 2**15 until both ends of the gradient are zero; returns the number of non-zero entries in the left
+        and in the right half.  On the GPU the probe runs on the exact-f32 kernels: the x6 kernels enter every operand as two
+        f16 pieces under a per-tensor scale, so a gradient entry far enough below its tensor's maximum becomes an exact zero
+        there -- and the tail of a receptive field is made of such entries ("Latent-space analysis").  Everything
+        the probe touches is put back: train / eval flags, the kernel mode, parameter gradients, the packed weights."""
+        import contextlib
+        from . import ops
+        modes = [(mod, mod.training) for mod in self.modules()]
+        gated = [mod for mod in self.modules() if hasattr(mod, "gru_state") or hasattr(mod, "temporal")]
+        device = next(iter(self.parameters())).device
+        exact = ops._ExactF32() if device.type == "cuda" else contextlib.nullcontext()
+        n = 2 ** 15
+        try:
+            self.eval()
+            for mod in gated:
+                mod.disable()
+            with torch.enable_grad(), exact:
+                while True:
+                    x = torch.randn(1, self.n_channels, n, requires_grad=True, device=device)
+                    if x.is_cuda:
+                        self.prepare_weights(reuse=True)
+                    z = self.encode(x)
+                    z = self.encoder.reparametrize(z)[0]
+                    y = self.decode(z)
+                    y[0, 0, n // 2].backward()
+                    assert x.grad is not None, "input has no grad"
+                    left_grad, right_grad = x.grad.detach().reshape(-1).chunk(2, 0)
+                    if bool(left_grad[0] == 0) and bool(right_grad[-1] == 0):
+                        break
+                    n *= 2
+            left = int((left_grad != 0).sum())
+            right = int((right_grad != 0).sum())
+        finally:
+            self._join_side()
+            self.zero_grad()
+            self.release_weights()
+            for mod in gated:
+                mod.enable()
+            for mod, training in modes:
+                mod.training = training
+        return left, right
+
+    # ---- rave/model.py:445-488
+    def validation_epoch_end(self, out):
+        """``out``: the list of validation_step results of the epoch.  Fills ``receptive_field`` the first time (any model), then
+        -- ``latent_analysis=True``, before the GAN phase, variational encoder -- ``latent_mean`` / ``latent_pca`` /
+        ``fidelity`` from the posterior means in ``out`` (rave_amd.latent.LatentAnalysis: one HIP call per batch, no
+        concatenation, one small device-to-host copy) and the reference's ``fidelity_p`` log values into ``self.logged``.
+        The reference's audio logging is not restated."""
+        if not int(self.receptive_field.sum()):
+            lrf, rrf = self.measure_receptive_field()
+            self.receptive_field[0] = lrf
+            self.receptive_field[1] = rrf
+            self.__dict__.pop("_rf_host", None)       # training_step's host copy: the next step reads the buffer again
+        if not len(out):
+            return
+        if self.warmed_up or not isinstance(self.encoder, blocks.VariationalEncoder) or not self.latent_analysis:
+            return
+        from .latent import LatentAnalysis
+        analysis = LatentAnalysis()
+        for _, mean in out:
+            analysis.update(mean)
+        result = analysis.finish()
+        if result is None:
+            return
+        latent_mean, components, fidelity = result
+        self.latent_mean.copy_(latent_mean)
+        self.latent_pca.copy_(components)
+        self.fidelity.copy_(fidelity)
+        logged = dict(self.logged)
+        for p in (.8, .9, .95, .99):
+            # rave/model.py:483-488: np.argmax(var > p), the first index whose cumulative share exceeds p (var is f32 there too)
+            logged[f"fidelity_{p}"] = float(torch.argmax((fidelity > p).to(torch.uint8)))
+        self.logged = logged
+
 
 class LinearLR:
     """torch.optim.lr_scheduler.LinearLR(start_factor, end_factor, total_iters) in closed form:
@@ -697,7 +782,7 @@ V2_DILATIONS = [[1, 3, 9], [1, 3, 9], [1, 3, 9], [1, 3]]
 
 
 def build_v1(n_channels: int = 1, capacity: int = 64, ratios=(4, 4, 4, 2), latent_size: int = 128,
-             n_band: int = 16, sampling_rate: int = 44100, use_noise: bool = True) -> "RAVE":
+             n_band: int = 16, sampling_rate: int = 44100, use_noise: bool = True, latent_analysis: bool = False) -> "RAVE":
     """configs/v1.gin: v1 Encoder (BatchNorm) / Generator (ResidualStack, loudness + noise branches),
     multi-scale discriminator only, feature matching L1 x10, discriminator every 2nd step."""
     cc.set_default_padding_mode("centered")
@@ -718,7 +803,7 @@ def build_v1(n_channels: int = 1, capacity: int = 64, ratios=(4, 4, 4, 2), laten
                 discriminator=msd, phase_1_duration=1000000, gan_loss=losses.hinge_gan, valid_signal_crop=False,
                 feature_matching_fun=partial(losses.mean_difference, norm="L1"), num_skipped_features=0,
                 audio_distance=dist, multiband_audio_distance=dist, weights={"feature_matching": 10},
-                update_discriminator_every=2, n_channels=n_channels, n_bands=n_band)
+                update_discriminator_every=2, n_channels=n_channels, n_bands=n_band, latent_analysis=latent_analysis)
 
 
 def build_v2_small(**kw) -> "RAVE":
@@ -735,7 +820,8 @@ def build_v2(n_channels: int = 1, capacity: int = 96, ratios=(4, 4, 4, 2), laten
              encoder_kind: str = "variational", noise_augmentation: int = 0, num_quantizers: int = 16,
              codebook_size: int = 1024, log_epsilon: float = 1e-7, num_skipped_features: int = 1,
              spectral_capacity: int = 32, gru_layers: int = 0, mel_input: bool = False, n_fft: int = 2048,
-             hop_length: int = 256, n_mels: int = 128, encoder_ratios=(2, 2, 2), encoder_dilations=(1,)) -> RAVE:
+             hop_length: int = 256, n_mels: int = 128, encoder_ratios=(2, 2, 2), encoder_dilations=(1,),
+             latent_analysis: bool = False) -> RAVE:
     """configs/v1.gin + configs/v2.gin transcribed (cf. oracle/ref_models.py for the citations).
     ``snake`` / ``adain`` add the generator-side overlays of configs/v3.gin (snake.gin: every activation
     -> blocks.Snake; adain.gin: AdaptiveInstanceNormalization before every unit); ``causal`` =
@@ -745,7 +831,9 @@ def build_v2(n_channels: int = 1, capacity: int = 96, ratios=(4, 4, 4, 2), laten
     ``gru_layers`` > 0 puts blocks.GRU in front of the decoder (the generator half of configs/hybrid.gin:33-38).
     ``mel_input`` is the encoder half (hybrid.gin:11-31, 40-42): RAVE.input_mode = "mel" with rave_amd.MelSpectrogram
     (``n_fft``, ``hop_length``, ``n_mels``, normalized) and EncoderV2(data_size = n_mels * n_channels as the reference's
-    encoder computes it, ``encoder_ratios``, ``encoder_dilations``); the decoder keeps ``ratios`` / ``dilations``."""
+    encoder computes it, ``encoder_ratios``, ``encoder_dilations``); the decoder keeps ``ratios`` / ``dilations``.
+    ``latent_analysis`` registers the reference's ``latent_pca`` / ``latent_mean`` / ``fidelity`` buffers (rave/model.py:196-198),
+    which ``validation_epoch_end`` then fills; off by default, the state_dict keys are then unchanged."""
     ratios = list(ratios)
     spectrogram = None
     if mel_input:
@@ -823,7 +911,7 @@ def build_v2(n_channels: int = 1, capacity: int = 96, ratios=(4, 4, 4, 2), laten
                  num_skipped_features=num_skipped_features, audio_distance=dist, multiband_audio_distance=dist,
                  weights={"feature_matching": 20}, update_discriminator_every=update_discriminator_every,
                  n_channels=n_channels, n_bands=n_band, spectrogram=spectrogram,
-                 input_mode="mel" if mel_input else "pqmf")
+                 input_mode="mel" if mel_input else "pqmf", latent_analysis=latent_analysis)
     cc.set_default_padding_mode("centered")
     blocks.set_dilated_unit_activation(None)
     return model
