@@ -228,6 +228,18 @@ int rh_conv1d_bwd_weight_kernel_family(const rh_conv1d_desc* d);
  * whole weight tensor = wgrad_x6_wide_kernel, whose workgroups == K slices), workgroups, K slices, 1 if the input is staged once
  * per position} of the launch rh_conv1d_bwd_weight_f32 would issue under the present RH_WGRAD_X6_* switches; zeros otherwise. */
 int rh_conv1d_bwd_weight_plan_info(const rh_conv1d_desc* d, int32_t* out4);
+/* Diagnostics (host only, nothing is launched): which kernel INSTANCE rh_conv1d_bwd_weight_f32 would launch now for this
+ * descriptor, for dy / x pointers that are (1) or are not (0) 16-byte aligned and with (1) or without (0) both range slots
+ * armed, under the present RH_WGRAD_X6_* switches -- answered by the planner and instance selection the launch itself runs.
+ *   out16[0] = family (as rh_conv1d_bwd_weight_kernel_family; -1 = an empty or invalid geometry), then
+ *   family 1: {1, wide, NW (wide) or tm, wm (0 = wide), AV, PART, PL, Z, steps_per_z, total_steps, workgroup-tile rows,
+ *              workgroup-tile columns, steps_per_b, p8, chmax (both 0 without PL), row tiles * column tiles}
+ *              = wgrad_x6_wide_kernel<NW, PL> or wgrad_x6_kernel<tm, wm, 4 / wm, AV, PART, PL>; a step is 32 positions
+ *   family 0: {0, bm, bn, dma (1 = wgrad_dma_kernel, 0 = wgrad_kernel), vec, LeakyReLU operand (0 none, 1 R, 2 S), rk, Z,
+ *              chunks_per_z, total_chunks, chunks_per_b, nc_max, activation of R, activation of S, waves, row tiles * column tiles}
+ *   family 2: {2, 0 ...} (conv_smallc.hip) */
+int rh_conv1d_bwd_weight_instance_info(const rh_conv1d_desc* d, int dy_aligned16, int x_aligned16, int ranges_armed,
+                                       int32_t* out16);
 
 /* dx = act'(x) * conv_bwd_data(dy) + add.   `x` is the forward input (needed when act != NONE),
  * `add` (B,c_in,l_in*inner) may be NULL (residual-branch gradient). */

@@ -654,9 +654,23 @@ WPlan plan(const WgradP& p) {
 
 inline unsigned magic_of(int d) { return d <= 1 ? 0u : (unsigned)(((1ull << 32) + d - 1) / (unsigned long long)d); }
 
-template <int TM, int TN, int WM, int WN>
-int launch_w(WgradP& p, const WPlan& w, hipStream_t stream) {
-    constexpr int BM = TM * WM * 32, BN = TN * WN * 32;
+// The five tile shapes <TM, TN, WM, WN> of the two kernels, by the plan's workgroup tile (rh_wgrad_run instantiates exactly these).
+struct WShape { int tm, tn, wm, wn; };
+WShape w_shape(const WPlan& w) {
+    if (w.bm == 32) return WShape{1, 2, 1, 4};
+    if (w.bm == 64) return WShape{2, 1, 1, 4};
+    if (w.bm == 96 && w.bn == 96) return WShape{3, 1, 1, 3};
+    if (w.bm == 96) return WShape{3, 1, 1, 4};
+    return WShape{2, 2, 2, 2};
+}
+
+// The instance of a plan and a tile shape: which kernel, and for wgrad_dma_kernel the staging (vec) and which operand carries
+// LeakyReLU (0 none, 1 R, 2 S).  w_configure fills the launch fields of p for it; launch_w launches what it says, and
+// rh_conv1d_bwd_weight_instance_info reports it.
+struct WInst { int dma, vec, leaky; size_t lds; };
+
+WInst w_configure(WgradP& p, const WPlan& w, const WShape& sh) {
+    const int BM = sh.tm * sh.wm * 32, BN = sh.tn * sh.wn * 32, NWV = sh.wm * sh.wn;
     p.rk = w.rk;
     p.chunks_per_b = w.chunks_per_b;
     p.total_chunks = w.total_chunks;
@@ -679,8 +693,8 @@ int launch_w(WgradP& p, const WPlan& w, hipStream_t stream) {
                 p.pr = w.rk + 4;                       // one pad float4 per row: row stride = 4 (mod 32) banks
                 p.ps = ((s_width + 3) & ~3) + 4;
                 if ((p.ps & 31) == 0) p.ps += 4;
-                const int ni_r = rh_cdiv(BM * (p.pr >> 2), 64 * WM * WN);
-                const int ni_s = rh_cdiv(p.nc_max * (p.ps >> 2), 64 * WM * WN);
+                const int ni_r = rh_cdiv(BM * (p.pr >> 2), 64 * NWV);
+                const int ni_s = rh_cdiv(p.nc_max * (p.ps >> 2), 64 * NWV);
                 if (ni_r > 12 || ni_s > 12) p.vec = 0;
             }
             if (!p.vec) {
@@ -698,25 +712,34 @@ int launch_w(WgradP& p, const WPlan& w, hipStream_t stream) {
             p.r_bytes = (unsigned)rb;
             p.s_bytes = (unsigned)sbytes;
             const size_t lds = sizeof(float) * 2 * (size_t)p.stage_floats;
-            if (lds <= 160 * 1024 && (unsigned)p.s_floats < (1u << 15)) {
-                dim3 grid(w.ct, w.mt, w.Z);
-                auto go = [&](auto kern) {
-                    static std::once_flag once;
-                    std::call_once(once, [&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-                    rh_launch_main(kern, grid, dim3(WM * WN * 64), lds, stream, p);
-                };
-                if (p.r_act == RH_ACT_LEAKY) go(wgrad_dma_kernel<TM, TN, WM, WN, true, false>);
-                else if (p.s_act == RH_ACT_LEAKY) go(wgrad_dma_kernel<TM, TN, WM, WN, false, true>);
-                else go(wgrad_dma_kernel<TM, TN, WM, WN, false, false>);
-                return rh_check_launch("conv1d_bwd_weight(dma)");
-            }
+            if (lds <= 160 * 1024 && (unsigned)p.s_floats < (1u << 15))
+                return WInst{1, p.vec, p.r_act == RH_ACT_LEAKY ? 1 : (p.s_act == RH_ACT_LEAKY ? 2 : 0), lds};
         }
     }
+    p.vec = 0;
     p.pr = (w.rk * p.inner) | 1;
     p.ps = (((w.rk - 1) * p.is + (p.maxoff - p.minoff) + 1) * p.inner) | 1;
     p.nc_max = (BN - 1) / p.T + 2;
     if (p.nc_max > p.C) p.nc_max = p.C;
-    const size_t lds = sizeof(float) * ((size_t)BM * p.pr + (size_t)p.nc_max * p.ps);
+    return WInst{0, 0, 0, sizeof(float) * ((size_t)BM * p.pr + (size_t)p.nc_max * p.ps)};
+}
+
+template <int TM, int TN, int WM, int WN>
+int launch_w(WgradP& p, const WPlan& w, hipStream_t stream) {
+    const WInst in = w_configure(p, w, WShape{TM, TN, WM, WN});
+    const size_t lds = in.lds;
+    if (in.dma) {
+        dim3 grid(w.ct, w.mt, w.Z);
+        auto go = [&](auto kern) {
+            static std::once_flag once;
+            std::call_once(once, [&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
+            rh_launch_main(kern, grid, dim3(WM * WN * 64), lds, stream, p);
+        };
+        if (in.leaky == 1) go(wgrad_dma_kernel<TM, TN, WM, WN, true, false>);
+        else if (in.leaky == 2) go(wgrad_dma_kernel<TM, TN, WM, WN, false, true>);
+        else go(wgrad_dma_kernel<TM, TN, WM, WN, false, false>);
+        return rh_check_launch("conv1d_bwd_weight(dma)");
+    }
     RH_REQUIRE(lds <= 160 * 1024, RH_ERR_UNSUPPORTED, "conv1d_bwd_weight: tile needs %zu B of LDS", lds);
     auto kern = wgrad_kernel<TM, TN, WM, WN>;
     static std::once_flag once;
@@ -758,6 +781,34 @@ extern "C" int rh_conv1d_bwd_weight_plan_info(const rh_conv1d_desc* d, int32_t* 
     alignas(16) static const float dummy[4] = {0.f, 0.f, 0.f, 0.f};
     p.R = dummy; p.S = dummy;
     (void)rh_wgrad_x6_plan_info(p, out4);
+    return RH_OK;
+}
+
+bool rh_wgrad_x6_instance_info(const WgradP& w, bool armed, int32_t* out16);
+
+// Which kernel instance rh_wgrad_run would launch: the same three questions in the same order, answered by the code the launch
+// runs (rh_smallc_wgrad_eligible; plan_wx6 + wx6_inst_of; plan + w_shape + w_configure).
+extern "C" int rh_conv1d_bwd_weight_instance_info(const rh_conv1d_desc* d, int dy_aligned16, int x_aligned16, int ranges_armed,
+                                                  int32_t* out16) {
+    if (!d || !out16) return RH_ERR_INVALID;
+    for (int i = 0; i < 16; ++i) out16[i] = 0;
+    out16[0] = -1;
+    if (d->batch <= 0 || d->l_in <= 0 || d->l_out <= 0 || d->inner <= 0 || d->kernel <= 0 || d->kernel > kMaxTaps) return RH_OK;
+    WgradP p{};
+    fill(d, &p);
+    if (rh_smallc_wgrad_eligible(d)) { out16[0] = 2; return RH_OK; }
+    alignas(16) static const float dummy[8] = {};
+    const float* const dy = dummy + (dy_aligned16 ? 0 : 1);
+    const float* const x = dummy + (x_aligned16 ? 0 : 1);
+    if (!d->transposed) { p.R = dy; p.S = x; }
+    else                { p.R = x; p.S = dy; }
+    if (d->act != RH_ACT_SNAKE && rh_wgrad_x6_instance_info(p, !RH_X6_F16 || ranges_armed != 0, out16)) return RH_OK;
+    const WPlan w = plan(p);
+    const WShape sh = w_shape(w);
+    const WInst in = w_configure(p, w, sh);
+    const int32_t v[16] = {0, w.bm, w.bn, in.dma, in.vec, in.leaky, w.rk, w.Z, w.chunks_per_z, w.total_chunks, w.chunks_per_b,
+                           p.nc_max, p.r_act, p.s_act, sh.wm * sh.wn, w.mt * w.ct};
+    for (int i = 0; i < 16; ++i) out16[i] = v[i];
     return RH_OK;
 }
 
@@ -896,11 +947,14 @@ int rh_wgrad_run(const rh_conv1d_desc* d, const float* dy, const float* x, const
                "conv1d_bwd_weight: workspace %lld B < %lld B", (long long)ws_bytes, (long long)need);
     p.out = w.Z > 1 ? (float*)ws : dw;
     int e;
-    if (w.bm == 32) e = launch_w<1, 2, 1, 4>(p, w, stream);
-    else if (w.bm == 64) e = launch_w<2, 1, 1, 4>(p, w, stream);
-    else if (w.bm == 96 && w.bn == 96) e = launch_w<3, 1, 1, 3>(p, w, stream);
-    else if (w.bm == 96) e = launch_w<3, 1, 1, 4>(p, w, stream);
-    else e = launch_w<2, 2, 2, 2>(p, w, stream);
+    const WShape sh = w_shape(w);
+    const auto is = [&](int tm, int tn, int wm, int wn) { return sh.tm == tm && sh.tn == tn && sh.wm == wm && sh.wn == wn; };
+    if (is(1, 2, 1, 4)) e = launch_w<1, 2, 1, 4>(p, w, stream);
+    else if (is(2, 1, 1, 4)) e = launch_w<2, 1, 1, 4>(p, w, stream);
+    else if (is(3, 1, 1, 3)) e = launch_w<3, 1, 1, 3>(p, w, stream);
+    else if (is(3, 1, 1, 4)) e = launch_w<3, 1, 1, 4>(p, w, stream);
+    else if (is(2, 2, 2, 2)) e = launch_w<2, 2, 2, 2>(p, w, stream);
+    else RH_REQUIRE(false, RH_ERR_UNSUPPORTED, "conv1d_bwd_weight: no kernel for tile shape %d %d %d %d", sh.tm, sh.tn, sh.wm, sh.wn);
     if (e) return e;
     if (w.Z > 1) {
         if (tail) {

@@ -24,8 +24,9 @@
 //
 // Two tile shapes (wx6_choose_tile chooses by the layer):
 //   * wgrad_x6_kernel: four waves, workgroup tile 32 TM WM rows x 64 WN columns, wave tile 32 TM x 64, one LDS stage, two
-//     barriers per step, two or three workgroups per CU whose phases interleave -- every layer with more than 96 gradient rows
-//     or more than 288 columns;
+//     barriers per step, two or three workgroups per CU whose phases interleave -- every eligible layer that does not take the
+//     wide tile: 32 ... 64 gradient rows (on rows of at most 1024 positions), more than 96 rows, or more than 288 columns;
+//     40 instances (tests/wgrad_matrix.py runs each of them, and each of the 8 wide ones, against f64);
 //   * wgrad_x6_wide_kernel: ONE workgroup tile over all rows (65 ... 96) and all columns (<= 288), one wave per 32 columns
 //     (3, 4, 6 or 9 waves, wave tile 96 x 32) -- the C = 96 layers and the stem of the v2 model.  RH_WGRAD_X6_WIDE=0 sends
 //     them to the 4-wave kernel.
@@ -365,7 +366,8 @@ __device__ __forceinline__ void wx6_store_tile(const Wx6P& p, float* __restrict_
 // PL ("planes", round 5; Wx6STasks): the S operand of a stride-1 layer with several taps is staged ONCE PER POSITION.  A tap is an
 // address offset; nothing is converted per tap: C = 96, k = 3 converts
 // (96 + 91) x 32 samples per step instead of (96 + 256) x 32, dilation 9 (96 + 134) x 32; C >= 192 (192 + 46) instead of
-// (192 + 128).  Same products in the same order: bit-identical weight gradients (tests/test_gpu_dispatch.py).
+// (192 + 128).  Same products in the same order: bit-identical weight gradients (tests/test_gpu_dispatch.py; at the tile edges and
+// tails: tests/test_gpu_wgrad_matrix.py).
 // MEASURED SLOWER from C = 192 on and therefore opt-in there (profiles/round5_negative_wgrad_planes.txt, round 6: plan_wx6): the
 // 64-row variants need 158-169 registers, two workgroups per CU instead of three where they pass 168 (forced under it they spill).
 template <int TM, int WM, int WN, bool AV, bool PART, bool PL>
@@ -714,20 +716,34 @@ Wx6Launch wx6_pick(int v, F f) {
     return r;
 }
 
-// The instance of a plan: wgrad_x6_wide_kernel<NW, PL> (8) or wgrad_x6_kernel<TM, WM, 4 / WM, AV, PART, PL> (40: the plan asks for
-// no plane staging with TM = 1, and there is no such instance).
-Wx6Launch wx6_instance(const Wx6P& p, const Wx6Plan& pl) {
-    if (pl.nw > 0)
-        return wx6_pick<3, 4, 6, 9>(pl.nw, [&](auto NW) {
-            return wx6_pick<0, 1>(pl.planes, [&](auto PL) -> Wx6Launch { return launch_wx6<wgrad_x6_wide_kernel<decltype(NW)::value, decltype(PL)::value != 0>>; });
+// The instance of a plan, by name: what wx6_instance turns into a kernel and rh_wgrad_x6_instance_info reports.
+struct Wx6Inst {
+    int nw;                  // > 0: wgrad_x6_wide_kernel<nw, pl>; 0: wgrad_x6_kernel<tm, wm, 4 / wm, av, part, pl>
+    int tm, wm;
+    int av;                  // rows of R are 16-byte aligned (wide tile: the uniform p.av, no template argument)
+    int part;                // 32-column MFMA tiles do not fill the last workgroup tile (4-wave kernel only)
+    int pl;
+};
+
+Wx6Inst wx6_inst_of(const Wx6P& p, const Wx6Plan& pl) {
+    if (pl.nw > 0) return Wx6Inst{pl.nw, 3, 1, p.av, 0, pl.planes};
+    const int av = p.r_row % 4 == 0 && ((uintptr_t)p.R & 15) == 0;
+    const int part = rh_cdiv(p.N, 32) % (2 * (4 / pl.wm)) != 0;
+    return Wx6Inst{0, pl.tm, pl.wm, av, part, pl.planes && pl.tm >= 2};
+}
+
+// The kernel of an instance: wgrad_x6_wide_kernel<NW, PL> (8) or wgrad_x6_kernel<TM, WM, 4 / WM, AV, PART, PL> (40: the plan asks
+// for no plane staging with TM = 1, and there is no such instance).
+Wx6Launch wx6_instance(const Wx6Inst& in) {
+    if (in.nw > 0)
+        return wx6_pick<3, 4, 6, 9>(in.nw, [&](auto NW) {
+            return wx6_pick<0, 1>(in.pl, [&](auto PL) -> Wx6Launch { return launch_wx6<wgrad_x6_wide_kernel<decltype(NW)::value, decltype(PL)::value != 0>>; });
         });
-    const int av = p.r_row % 4 == 0 && ((uintptr_t)p.R & 15) == 0;             // rows of R are 16-byte aligned
-    const int part = rh_cdiv(p.N, 32) % (2 * (4 / pl.wm)) != 0;                // 32-column MFMA tiles do not fill the last workgroup tile
-    return wx6_pick<1, 2, 3>(pl.tm, [&](auto TM) {
-        return wx6_pick<1, 2>(pl.wm, [&](auto WM) {
-            return wx6_pick<0, 1>(av, [&](auto AV) {
-                return wx6_pick<0, 1>(part, [&](auto PART) {
-                    return wx6_pick<0, 1>(pl.planes, [&](auto PL) -> Wx6Launch {
+    return wx6_pick<1, 2, 3>(in.tm, [&](auto TM) {
+        return wx6_pick<1, 2>(in.wm, [&](auto WM) {
+            return wx6_pick<0, 1>(in.av, [&](auto AV) {
+                return wx6_pick<0, 1>(in.part, [&](auto PART) {
+                    return wx6_pick<0, 1>(in.pl, [&](auto PL) -> Wx6Launch {
                         constexpr int tm = decltype(TM)::value, wm = decltype(WM)::value;
                         constexpr bool planes = decltype(PL)::value != 0 && tm >= 2;
                         return launch_wx6<wgrad_x6_kernel<tm, wm, 4 / wm, decltype(AV)::value != 0, decltype(PART)::value != 0, planes>>;
@@ -764,6 +780,24 @@ bool rh_wgrad_x6_plan_info(const WgradP& w, int32_t* out4) {
     return true;
 }
 
+// Diagnostics (rh_conv1d_bwd_weight_instance_info): the instance rh_wgrad_x6_launch would launch for w (w.R carries the
+// alignment of R) -- plan_wx6 + wx6_inst_of, the launch's own code.  armed = the call has its two range slots.  out16 =
+// {1, wide, NW or tm, wm, AV, PART, PL, Z, steps_per_z, total_steps, tile rows, tile columns, steps_per_b, p8, chmax, row tiles *
+// column tiles}; false = the call does not take this path.
+bool rh_wgrad_x6_instance_info(const WgradP& w, bool armed, int32_t* out16) {
+    Wx6P p;
+    Wx6Plan pl{};
+    static const unsigned any_range[kRangeSlotWords] = {};
+    const unsigned* const range = armed ? any_range : nullptr;
+    if (!plan_wx6(w, &p, &pl, range, range)) return false;
+    const Wx6Inst in = wx6_inst_of(p, pl);
+    const int32_t v[16] = {1, in.nw > 0, in.nw > 0 ? in.nw : in.tm, in.nw > 0 ? 0 : in.wm, in.av, in.part, in.pl, pl.Z, pl.steps_per_z,
+                           p.total_steps, in.nw > 0 ? 96 : 32 * in.tm * in.wm, in.nw > 0 ? 32 * in.nw : 64 * (4 / in.wm), p.steps_per_b,
+                           in.pl ? p.p8 : 0, in.pl ? p.chmax : 0, pl.rt * pl.ct};
+    for (int i = 0; i < 16; ++i) out16[i] = v[i];
+    return true;
+}
+
 // Returns RH_OK with *used = false when the geometry does not fit this path.  ws must hold rh_wgrad_x6_workspace bytes.
 // rsum_out != null: also the row sums of R over (batch, position) -- the bias gradient when R = dy -- from the same pass
 // left_z != null and the K range was split: the weight partials stay UNREDUCED in ws ([Z][M][C*T], *left_z = Z) for a caller
@@ -779,7 +813,7 @@ int rh_wgrad_x6_launch(const WgradP& w, float* dw, float* rsum_out, void* ws, hi
     float* const rs_part = (float*)ws + (pl.Z > 1 ? (long)pl.Z * w.M * w.C * w.T : 0);
     p.rsum = rsum_out ? (pl.Z > 1 ? rs_part : rsum_out) : nullptr;
     const dim3 grid = pl.nw > 0 ? dim3(pl.Z) : dim3(pl.ct, pl.rt, pl.Z);
-    wx6_instance(p, pl)(grid, pl.nw > 0 ? 64 * pl.nw : 256, pl.lds, stream, p);
+    wx6_instance(wx6_inst_of(p, pl))(grid, pl.nw > 0 ? 64 * pl.nw : 256, pl.lds, stream, p);
     if (int e = rh_check_launch("conv1d_bwd_weight_x6")) return e;
     *used = true;
     if (pl.Z > 1) {

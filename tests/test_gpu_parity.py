@@ -150,7 +150,9 @@ CONV_CASES = [
     (2, 32, 32, 5, 3, 1, 1, (1, 1), 2, False, False),       # snake, sequence shorter than a tile
     # stride-1, C % 16 == 0: conv_x6_kernel (conv_x6.hip), forward and data gradient.  These four rows all plan to tm = 3
     # (round32(M) % 96 == 0); the planner also has tm = 2 (% 64) and tm = 1 (anything else) -- every tile shape, operand mode and
-    # K mode is run by tests/test_gpu_x6_matrix.py (table and coverage proof: tests/x6_matrix.py, tests/test_x6_matrix_host.py)
+    # K mode is run by tests/test_gpu_x6_matrix.py (table and coverage proof: tests/x6_matrix.py, tests/test_x6_matrix_host.py).
+    # The weight gradient of these shapes is compared here as a whole tensor only; every weight-gradient instance and edge is run
+    # by tests/test_gpu_wgrad_matrix.py (tests/wgrad_matrix.py, tests/test_wgrad_matrix_host.py)
     (2, 96, 96, 256, 3, 1, 9, (9, 9), 1, False, False),     # dilated k3 of a residual unit
     (3, 192, 96, 64, 3, 1, 3, (6, 0), 1, True, True),       # causal pad, batch folded, bias + residual
     (2, 96, 192, 1024, 1, 1, 1, (0, 0), 0, False, False),   # pointwise, no activation

@@ -6,6 +6,10 @@ column.  So with the K slicing of the 4-wave plan (``RH_WGRAD_X6_WIDE=2``) the w
 (``RH_WGRAD_X6_WIDE=0``), for the weight and the bias gradient; with its own slicing it stays within 2e-6 (relative L2) of the
 exact-f32 MFMA kernels (``RH_WGRAD_X6=0``) and two runs of one call give the same bits.  Which kernel and which slicing a call
 takes is read from the library (``rh_conv1d_bwd_weight_plan_info``), so that none of this compares the 4-wave path with itself.
+
+These are the workload's shapes through autograd, compared among the project's own kernels.  Every instance of both kernels
+against an independent f64 reference, slice by slice and at the tile edges, is tests/test_gpu_wgrad_matrix.py (table:
+tests/wgrad_matrix.py, coverage proof: tests/test_wgrad_matrix_host.py).
 """
 import importlib.util
 import os
