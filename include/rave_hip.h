@@ -389,6 +389,27 @@ int rh_conv2d_bwd_data_f32(const rh_conv2d_desc* d, const float* dy, const float
  * out[16] = {family: 0 f32-input MFMA, 1 bf16x6 (conv2d_x6.hip), 2 vector ALU (conv2d_smallm.hip: <= 4 output rows); tm; tn; conversion tasks per thread; TR; TQ; nb; LDS bytes;
  *            workgroups; PH; PW; P (patch positions); largest tap offset in the patch; phases; row tiles; column tiles} */
 int rh_conv2d_plan_info(const rh_conv2d_desc* d, int32_t which, int64_t* out);
+/* Diagnostics (host only, nothing is launched): which kernel INSTANCE rh_conv2d_fwd_f32 (which = 0), rh_conv2d_bwd_data_f32 (1) or
+ * rh_conv2d_bwd_weight_f32 (2) would launch now for this descriptor (its `act` included: a backward call with act != NONE takes the
+ * fused-derivative paths), given what a descriptor cannot carry -- range slots armed (1) or not (0); the activation pointers 16-byte
+ * aligned (1) or only 4-byte aligned (0); the same for the packed operand; the bytes of workspace offered to the weight gradient
+ * (ignored for which < 2) -- under the switches that are read at every call (RH_CONV2D_X6, RH_CONV2D_SMALLM, RH_CONV_X6,
+ * RH_WGRAD2D_X6; RH_WGRAD_X6, the switch of the 1-D weight gradient, also turns wgrad2d_x6_kernel off and is read per call too).
+ * Answered by the selection and planning code the launch itself runs.  out[24]:
+ *   out[0]  kernel: 0 conv2d_x6_kernel, 1 conv2d_dma_kernel, 2 conv2d_igemm_kernel, 3 conv2d_smallm_kernel,
+ *           4 conv2d_smallc_fwd_kernel, 5 wgrad2d_x6_kernel, 6 wgrad2d_dma_kernel, 7 wgrad2d_kernel; -1 = an empty batch
+ *   out[1..4] template arguments: x6 {TM, TN, NQ}; dma / igemm / wgrad2d {TM, TN, WM, WN}; smallm {KH, MM, FLIP}; smallc {KH};
+ *           wgrad2d_x6 {NQX, SW}; wgrad2d_dma {TN}
+ *   convolutions (which < 2): out[5..] = {TR, TQ, nb, PH, PW, ck (channels per staged chunk), phases, grid x, grid y, grid z,
+ *           LDS bytes, row tiles, column tiles, family as rh_conv2d_plan_info, for conv2d_igemm_kernel why conv2d_dma_kernel did not
+ *           take the call: 1 fused derivative, 2 a tensor of 2 GB, 3 the patch exceeds the DMA slots even at TR = 1 and TQ = 16,
+ *           4 LDS, 5 grid, 6 RH_CONV2D_NODMA}
+ *   weight gradient: out[5..] = {TR (x6) or rk, TQ (x6) or wk, Z, chunks_per_z (0 for x6), channel groups (x6) or workgroup tiles,
+ *           nc_max (x6: channels of the fullest group), LDS bytes, workspace bytes the launch uses behind the bias scratch (0 when
+ *           Z == 1), bytes of bias scratch in front, tiles (x6) or chunks in all, PH, patch pitch, 0, family as
+ *           rh_conv2d_bwd_weight_kernel_family, 1 = the workspace offered is too small for this launch: the call fails} */
+int rh_conv2d_instance_info(const rh_conv2d_desc* d, int32_t which, int32_t ranges_armed, int32_t data_aligned16,
+                            int32_t packed_aligned16, int64_t workspace_bytes, int64_t* out24);
 /* 1 = rh_conv2d_bwd_weight_f32 runs this geometry (act == NONE) on the bf16 matrix cores (wgrad2d_x6.hip), else 0. */
 int rh_conv2d_bwd_weight_kernel_family(const rh_conv2d_desc* d);
 int64_t rh_conv2d_workspace_bytes(const rh_conv2d_desc* d);

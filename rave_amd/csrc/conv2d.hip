@@ -20,15 +20,19 @@
 int64_t rh_wgrad2d_x6_workspace(const rh_conv2d_desc* d);
 int rh_wgrad2d_x6_launch(const rh_conv2d_desc* d, const float* dy, const float* x, float* dw, void* ws, int64_t ws_bytes,
                          hipStream_t stream, bool* used, const unsigned* dy_range, const unsigned* x_range);
+bool rh_wgrad2d_x6_plan_as_called(const rh_conv2d_desc* d, const float* dy, const float* x, const void* ws, int64_t ws_bytes,
+                                  const unsigned* dy_range, const unsigned* x_range, long* out12);
 // conv2d_smallm.hip: vector-ALU kernels for convolutions with <= 4 output rows (first-layer data gradient, scoring conv)
 bool rh_conv2d_smallm_eligible(const rh_conv2d_desc* d, int which);
 int rh_conv2d_smallm_launch(const rh_conv2d_desc* d, int which, const float* in, const float* wp, const float* bias, float* out,
                             hipStream_t stream);
+void rh_conv2d_smallm_plan_info(const rh_conv2d_desc* d, int which, long* out12);
 
 // conv2d_smallc.hip: vector-ALU forward for <= 4 input channels (the first conv of the spectral discriminators' stacks)
 bool rh_conv2d_smallc_fwd_eligible(const rh_conv2d_desc* d);
 int rh_conv2d_smallc_fwd_launch(const rh_conv2d_desc* d, const float* x, const float* wp_fwd, const float* bias, float* y,
                                 hipStream_t stream);
+void rh_conv2d_smallc_fwd_plan_info(const rh_conv2d_desc* d, long* out9);
 
 namespace {
 
@@ -808,9 +812,31 @@ void fill_common(const Plan2& t, Conv2P* p, int C, int M) {
     }
 }
 
-template <int TM, int TN, int WM, int WN>
-int launch2(Conv2P& p, const Plan2& t, hipStream_t stream, const char* what) {
-    constexpr int BM = TM * WM * 32, BN = TN * WN * 32;
+// The four workgroup tiles of the f32-input family, by output rows: TM x TN MFMA tiles per wave, WM x WN waves.
+struct Tile2 {
+    int tm, tn, wm, wn;
+    int bm() const { return tm * wm * 32; }
+    int bn() const { return tn * wn * 32; }
+};
+
+inline Tile2 tile2_of(int M) {
+    if (M <= 32) return {1, 2, 1, 4};
+    if (M <= 64) return {2, 1, 1, 4};
+    if (M % 96 == 0) return {3, 1, 1, 4};
+    return {2, 2, 2, 2};
+}
+
+// A planned launch of conv2d_dma_kernel (dma) or conv2d_igemm_kernel on one of the four tiles; the tile plan itself is in Conv2P.
+struct Launch2 {
+    bool dma;
+    Tile2 tile;
+    size_t lds;
+    dim3 grid;
+};
+
+// Register-staged kernel: the plan of last resort (an error when even that does not fit).
+int plan2(Conv2P& p, const Plan2& t, const Tile2& tl, const char* what, Launch2* l) {
+    const int BM = tl.bm(), BN = tl.bn();
     p.TQ = pow2ceil(p.qcols) < BN ? pow2ceil(p.qcols) : BN;
     const int tr_cap = BN / p.TQ;
     p.TR = pow2ceil(p.rows) < tr_cap ? pow2ceil(p.rows) : tr_cap;
@@ -849,30 +875,23 @@ int launch2(Conv2P& p, const Plan2& t, hipStream_t stream, const char* what) {
     RH_REQUIRE((long)p.nb * ck * p.PH * p.PW < (1l << 20) && (long)maxtaps * ck * BM < (1l << 20), RH_ERR_UNSUPPORTED,
                "%s: tile too large", what);
     RH_REQUIRE(lds <= 160 * 1024, RH_ERR_UNSUPPORTED, "%s: tile needs %zu B of LDS", what, lds);
-    auto kern = conv2d_igemm_kernel<TM, TN, WM, WN>;
-    static std::once_flag once;
-    std::call_once(once, [&] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
-    });
     const long gx = (long)rh_cdiv(p.B, p.nb) * p.tiles_r * p.tiles_q;
     RH_REQUIRE(gx < (1l << 31), RH_ERR_UNSUPPORTED, "%s: grid too large", what);
-    dim3 grid((unsigned)gx, rh_cdiv(p.M, BM), p.nphase);
-    hipLaunchKernelGGL(kern, grid, dim3(WM * WN * 64), lds, stream, p);
-    return rh_check_launch(what);
+    l->dma = false;
+    l->tile = tl;
+    l->lds = lds;
+    l->grid = dim3((unsigned)gx, rh_cdiv(p.M, BM), p.nphase);
+    return RH_OK;
 }
 
-
-// LDS-DMA variant: returns RH_ERR_UNSUPPORTED (without setting a message the caller shows) when the geometry
-// does not fit its staging scheme; the caller then uses the register-staged kernel.
-template <int TM, int TN, int WM, int WN>
-int launch2_dma(Conv2P& p, const Plan2& t, hipStream_t stream, const char* what, bool* done) {
-    constexpr int BM = TM * WM * 32, BN = TN * WN * 32;
-    *done = false;
-    if (p.in_mul) return RH_OK;
-    const long in_b = (long)p.B * p.C * p.in_h * p.in_w * 4, w_b = 0;
-    (void)w_b;
-    if (in_b >= (1l << 31)) return RH_OK;
+// LDS-DMA variant: kDma, or why the geometry does not fit its staging scheme (the caller then plans the register-staged kernel):
+// a fused derivative, a tensor of 2 GB, a patch of more than 64 * kNI floats even at TR = 1 and TQ = 16, the LDS, the grid.
+enum { kDma = 0, kNoDmaFused, kNoDmaBytes, kNoDmaPatch, kNoDmaLds, kNoDmaGrid, kNoDmaOff };
+int plan2_dma(Conv2P& p, const Plan2& t, const Tile2& tl, Launch2* l) {
+    const int BM = tl.bm(), BN = tl.bn();
+    if (p.in_mul) return kNoDmaFused;
+    const long in_b = (long)p.B * p.C * p.in_h * p.in_w * 4;
+    if (in_b >= (1l << 31)) return kNoDmaBytes;
     int span_h = 0, span_w = 0, maxtaps = 1;
     long wfloats = 0;
     for (int i = 0; i < t.nphase; ++i) {
@@ -881,14 +900,14 @@ int launch2_dma(Conv2P& p, const Plan2& t, hipStream_t stream, const char* what,
         maxtaps = maxtaps > t.ntaps[i] ? maxtaps : t.ntaps[i];
         wfloats += (long)t.ntaps[i] * p.C * p.Mp;
     }
-    if (wfloats * 4 >= (1l << 31)) return RH_OK;
+    if (wfloats * 4 >= (1l << 31)) return kNoDmaBytes;
     int TQ = pow2ceil(p.qcols) < BN ? pow2ceil(p.qcols) : BN;
     int TR = pow2ceil(p.rows) < BN / TQ ? pow2ceil(p.rows) : BN / TQ;
     auto patch = [&](int tq_, int tr_) { return (long)((tr_ - 1) * p.is_h + span_h + 1) * ((tq_ - 1) * p.is_w + span_w + 1); };
     while (patch(TQ, TR) > 64 * kNI) {
         if (TR > 1) TR >>= 1;
         else if (TQ > 16) TQ >>= 1;
-        else return RH_OK;
+        else return kNoDmaPatch;
     }
     p.TQ = TQ; p.TR = TR;
     p.nb = BN / (TQ * TR);
@@ -920,54 +939,79 @@ int launch2_dma(Conv2P& p, const Plan2& t, hipStream_t stream, const char* what,
     p.wlds_floats = (maxtaps * ck * BM + 255) & ~255;
     p.stage_floats = p.wlds_floats + p.nb * ck * p.chp;
     const size_t lds = sizeof(float) * 2 * (size_t)p.stage_floats;
-    if (lds > 160 * 1024) return RH_OK;
+    if (lds > 160 * 1024) return kNoDmaLds;
     p.in_bytes = (unsigned)in_b;
     p.w_bytes = (unsigned)(wfloats * 4);
-    auto kern = conv2d_dma_kernel<TM, TN, WM, WN>;
-    static std::once_flag once;
-    std::call_once(once, [&] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
-    });
     const long gx = (long)rh_cdiv(p.B, p.nb) * p.tiles_r * p.tiles_q;
-    if (gx >= (1l << 31)) return RH_OK;
-    dim3 grid((unsigned)gx, rh_cdiv(p.M, BM), p.nphase);
-    hipLaunchKernelGGL(kern, grid, dim3(WM * WN * 64), lds, stream, p);
-    *done = true;
-    return rh_check_launch(what);
+    if (gx >= (1l << 31)) return kNoDmaGrid;
+    l->dma = true;
+    l->tile = tl;
+    l->lds = lds;
+    l->grid = dim3((unsigned)gx, rh_cdiv(p.M, BM), p.nphase);
+    return kDma;
+}
+
+// The family-0 launch of a forward / data gradient: the tile by output rows, the LDS-DMA kernel where its staging fits, else the
+// register-staged one.  The launch and rh_conv2d_instance_info both take their answer from here.
+int plan_conv2(Conv2P& p, const Plan2& t, const char* what, Launch2* l, int* no_dma_why) {
+    const Tile2 tl = tile2_of(p.M);
+    static const bool no_dma = getenv("RH_CONV2D_NODMA") != nullptr;
+    *no_dma_why = kNoDmaOff;
+    if (!no_dma) {
+        Conv2P q = p;
+        *no_dma_why = plan2_dma(q, t, tl, l);
+        if (*no_dma_why == kDma) {
+            p = q;
+            return RH_OK;
+        }
+    }
+    return plan2(p, t, tl, what, l);
 }
 
 template <int TM, int TN, int WM, int WN>
-int launch2_any(Conv2P& p, const Plan2& t, hipStream_t stream, const char* what) {
-    static const bool no_dma = getenv("RH_CONV2D_NODMA") != nullptr;
-    if (!no_dma) {
-        bool done = false;
-        Conv2P q = p;
-        if (int e = launch2_dma<TM, TN, WM, WN>(q, t, stream, what, &done)) return e;
-        if (done) return RH_OK;
+void go2(const Conv2P& p, const Launch2& l, hipStream_t stream) {
+    if (l.dma) {
+        auto kern = conv2d_dma_kernel<TM, TN, WM, WN>;
+        static std::once_flag once;
+        std::call_once(once, [&] {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      160 * 1024);
+        });
+        hipLaunchKernelGGL(kern, l.grid, dim3(WM * WN * 64), l.lds, stream, p);
+    } else {
+        auto kern = conv2d_igemm_kernel<TM, TN, WM, WN>;
+        static std::once_flag once;
+        std::call_once(once, [&] {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      160 * 1024);
+        });
+        hipLaunchKernelGGL(kern, l.grid, dim3(WM * WN * 64), l.lds, stream, p);
     }
-    return launch2<TM, TN, WM, WN>(p, t, stream, what);
 }
 
-int launch_conv2(Conv2P& p, const Plan2& t, hipStream_t stream, const char* what) {
-    if (p.B <= 0) return RH_OK;
-    if (p.M <= 32) return launch2_any<1, 2, 1, 4>(p, t, stream, what);
-    if (p.M <= 64) return launch2_any<2, 1, 1, 4>(p, t, stream, what);
-    if (p.M % 96 == 0) return launch2_any<3, 1, 1, 4>(p, t, stream, what);
-    return launch2_any<2, 2, 2, 2>(p, t, stream, what);
+int run_conv2(const Conv2P& p, const Launch2& l, hipStream_t stream, const char* what) {
+    switch (l.tile.tm * 10 + l.tile.tn) {
+        case 12: go2<1, 2, 1, 4>(p, l, stream); break;
+        case 21: go2<2, 1, 1, 4>(p, l, stream); break;
+        case 31: go2<3, 1, 1, 4>(p, l, stream); break;
+        default: go2<2, 2, 2, 2>(p, l, stream); break;
+    }
+    return rh_check_launch(what);
 }
 
+// A planned weight-gradient launch: wgrad2d_dma_kernel<tn> (dma) or wgrad2d_kernel on the bm-row tile of tile2_of
 struct W2Plan {
     int bm, bn, Z;
     size_t lds;
+    bool dma;
+    int tn;
 };
 
 W2Plan plan_w2(Wgrad2P& p) {
     W2Plan w{};
-    if (p.M <= 32) { w.bm = 32; w.bn = 256; }
-    else if (p.M <= 64) { w.bm = 64; w.bn = 128; }
-    else if (p.M % 96 == 0) { w.bm = 96; w.bn = 128; }
-    else { w.bm = 128; w.bn = 128; }
+    const Tile2 tl = tile2_of(p.M);
+    w.bm = tl.bm();
+    w.bn = tl.bn();
     const int ncols = p.C * p.T;
     p.nc_max = (w.bn - 1) / p.T + 2;
     if (p.nc_max > p.C) p.nc_max = p.C;
@@ -1113,6 +1157,27 @@ int launch_w2_dma(const Wgrad2P& p, const W2Plan& w, hipStream_t stream) {
     return rh_check_launch("conv2d_bwd_weight");
 }
 
+// The family-0 weight-gradient launch: the LDS-DMA kernel where its plan fits, else the generic kernel.  The launch and
+// rh_conv2d_instance_info both take their answer from here.
+W2Plan plan_w2_any(Wgrad2P& p) {
+    W2Plan w{};
+    int tn = 0;
+    if (plan_w2_dma(p, &w, &tn)) {
+        w.dma = true;
+        w.tn = tn;
+        return w;
+    }
+    return plan_w2(p);
+}
+
+int run_w2(const Wgrad2P& p, const W2Plan& w, hipStream_t stream) {
+    if (w.dma) return w.tn == 1 ? launch_w2_dma<1>(p, w, stream) : (w.tn == 2 ? launch_w2_dma<2>(p, w, stream) : launch_w2_dma<4>(p, w, stream));
+    if (w.bm == 32) return launch_w2<1, 2, 1, 4>(p, w, stream);
+    if (w.bm == 64) return launch_w2<2, 1, 1, 4>(p, w, stream);
+    if (w.bm == 96) return launch_w2<3, 1, 1, 4>(p, w, stream);
+    return launch_w2<2, 2, 2, 2>(p, w, stream);
+}
+
 void fill_w2(const rh_conv2d_desc* d, Wgrad2P* p) {
     *p = Wgrad2P{};
     p->B = d->batch; p->M = d->c_out; p->C = d->c_in; p->T = d->kh * d->kw;
@@ -1247,6 +1312,152 @@ extern "C" int rh_conv2d_pack_f32(const rh_conv2d_desc* d, const float* w, float
     return rh_pack_launch(a, b, (hipStream_t)stream, "conv2d_pack", w, d->c_out, (long)d->c_in * d->kh * d->kw);
 }
 
+namespace {
+
+// Kernels of rh_conv2d_instance_info (include/rave_hip.h)
+enum { K2_X6 = 0, K2_DMA, K2_IGEMM, K2_SMALLM, K2_SMALLC, K2_WX6, K2_WDMA, K2_WGRAD };
+constexpr int kInfo2 = 24;
+
+// Parameter blocks of a forward (which = 0) / data-gradient (1) call for both matrix-core families.  y: the activated output whose
+// act'(y) a data gradient with d->act != NONE folds into dy while staging.
+void fill_conv2(const rh_conv2d_desc* d, int which, const Plan2& t, const float* in, const float* y, const float* wp, const float* bias,
+                float* out, const unsigned* in_range, unsigned* out_range, Conv2P* pp, C2X* qq) {
+    Conv2P& p = *pp;
+    C2X& q = *qq;
+    p = Conv2P{};
+    const int C = which == 0 ? d->c_in : d->c_out, M = which == 0 ? d->c_out : d->c_in;
+    fill_common(t, &p, C, M);
+    fill_c2x(t, C, M, wp, &q);
+    p.in = in; p.wp = wp; p.out = out;
+    q.in = in; q.out = out;
+    p.B = q.B = d->batch;
+    if (which == 0) {
+        p.bias = q.bias = bias;
+        p.in_mul = nullptr;
+        p.in_h = q.in_h = d->h_in; p.in_w = q.in_w = d->w_in; p.out_h = q.out_h = d->h_out; p.out_w = q.out_w = d->w_out;
+        p.rows = q.rows = d->h_out; p.qcols = q.qcols = d->w_out;
+        p.is_h = q.is_h = d->sh; p.is_w = q.is_w = d->sw; p.os_h = q.os_h = 1; p.os_w = q.os_w = 1;
+        p.mul_act = RH_ACT_NONE; p.mul_slope = 0.f;
+        p.epi_act = q.out_act = d->act; p.epi_slope = q.out_slope = d->act_slope;
+    } else {
+        p.bias = q.bias = nullptr;
+        p.in_mul = d->act == RH_ACT_NONE ? nullptr : y;
+        p.in_h = q.in_h = d->h_out; p.in_w = q.in_w = d->w_out; p.out_h = q.out_h = d->h_in; p.out_w = q.out_w = d->w_in;
+        p.rows = q.rows = rh_cdiv(d->h_in, d->sh); p.qcols = q.qcols = rh_cdiv(d->w_in, d->sw);
+        p.is_h = q.is_h = 1; p.is_w = q.is_w = 1; p.os_h = q.os_h = d->sh; p.os_w = q.os_w = d->sw;
+        p.mul_act = d->act; p.mul_slope = d->act_slope;
+        p.epi_act = q.out_act = RH_ACT_NONE; p.epi_slope = q.out_slope = 0.f;
+    }
+    q.in_range = in_range; q.out_range = out_range;
+}
+
+// The one place that decides which kernel a forward (which = 0) / data-gradient (1) call runs, in the order it tries them: the
+// vector-ALU kernels, conv2d_x6_kernel, then family 0.  info == null: launch it (*x6 = conv2d_x6_kernel ran, which publishes the
+// output's range itself); else fill info[kInfo2] as include/rave_hip.h documents and launch nothing.
+int route_conv2(const rh_conv2d_desc* d, int which, const float* in, const float* y, const float* wp, const float* bias, float* out,
+                const unsigned* in_range, unsigned* out_range, hipStream_t stream, bool* x6, int64_t* info) {
+    *x6 = false;
+    const char* what = which == 0 ? "conv2d_fwd" : "conv2d_bwd_data";
+    Plan2 t;
+    build_plan2(d, which, &t);
+    Conv2P p;
+    C2X q;
+    fill_conv2(d, which, t, in, y, wp, bias, out, in_range, out_range, &p, &q);
+    if (rh_conv2d_smallm_eligible(d, which)) {
+        if (!info) return rh_conv2d_smallm_launch(d, which, in, wp, bias, out, stream);
+        long v[12];
+        rh_conv2d_smallm_plan_info(d, which, v);
+        info[0] = K2_SMALLM; info[1] = v[0]; info[2] = v[1]; info[3] = v[2];
+        info[5] = v[3]; info[6] = v[4]; info[7] = 1; info[8] = v[5]; info[9] = v[6]; info[10] = v[7]; info[11] = 1;
+        info[12] = v[9]; info[13] = 1; info[14] = 1; info[15] = v[8]; info[16] = v[10]; info[17] = v[11]; info[18] = 2;
+        return RH_OK;
+    }
+    if (which == 0 && rh_conv2d_smallc_fwd_eligible(d)) {
+        if (!info) return rh_conv2d_smallc_fwd_launch(d, in, wp, bias, out, stream);
+        long v[9];
+        rh_conv2d_smallc_fwd_plan_info(d, v);
+        info[0] = K2_SMALLC; info[1] = v[0];
+        info[5] = v[1]; info[6] = v[2]; info[7] = 1; info[8] = v[3]; info[9] = v[4]; info[10] = d->c_in; info[11] = 1;
+        info[12] = v[6]; info[13] = 1; info[14] = 1; info[15] = v[5]; info[16] = v[7]; info[17] = v[8]; info[18] = 2;
+        return RH_OK;
+    }
+    // exact f32 on the bf16 matrix cores where the geometry allows (C in blocks of 16): conv2d_x6.hip.  A data gradient takes it
+    // when the caller has folded act'(y) into dy (rave_amd.ops._Conv2dFn.backward).
+    if ((which == 0 || d->act == RH_ACT_NONE) && q.wq) {
+        if (!info) {
+            if (int e = rh_conv2d_x6_launch(q, stream, which == 0 ? "conv2d_fwd_x6" : "conv2d_bwd_data_x6", x6)) return e;
+            if (*x6) return RH_OK;
+        } else {
+            long v[15];
+            if (rh_conv2d_x6_plan_as_called(q, v)) {
+                info[0] = K2_X6; info[1] = v[0]; info[2] = v[1]; info[3] = v[2];
+                info[5] = v[3]; info[6] = v[4]; info[7] = v[5]; info[8] = v[8]; info[9] = v[9]; info[10] = 16; info[11] = t.nphase;
+                info[12] = v[10]; info[13] = v[11]; info[14] = v[12]; info[15] = v[6]; info[16] = v[13]; info[17] = v[14]; info[18] = 1;
+                return RH_OK;
+            }
+        }
+    }
+    if (p.B <= 0) return RH_OK;
+    Launch2 l{};
+    int no_dma_why = 0;
+    if (int e = plan_conv2(p, t, what, &l, &no_dma_why)) return e;
+    if (!info) return run_conv2(p, l, stream, what);
+    info[0] = l.dma ? K2_DMA : K2_IGEMM; info[1] = l.tile.tm; info[2] = l.tile.tn; info[3] = l.tile.wm; info[4] = l.tile.wn;
+    info[5] = p.TR; info[6] = p.TQ; info[7] = p.nb; info[8] = p.PH; info[9] = p.PW; info[10] = p.ck; info[11] = t.nphase;
+    info[12] = l.grid.x; info[13] = l.grid.y; info[14] = l.grid.z; info[15] = (int64_t)l.lds; info[16] = p.tiles_r; info[17] = p.tiles_q;
+    info[18] = 0;
+    info[19] = no_dma_why;
+    return RH_OK;
+}
+
+// The one place that decides which kernel a weight-gradient call runs: wgrad2d_x6_kernel where the geometry, the range slots and the
+// scratch offered allow, else family 0.  workspace: behind the bias scratch.  info as in route_conv2.
+int route_wgrad2(const rh_conv2d_desc* d, const float* dy, const float* ymul, const float* x, float* dw, void* workspace,
+                 int64_t workspace_bytes, const unsigned* dy_range, const unsigned* x_range, hipStream_t stream, int64_t* info) {
+    const long nw = (long)d->c_out * d->c_in * d->kh * d->kw;
+    if (d->act == RH_ACT_NONE) {      // (the caller has folded act'(y) into dy) -- bf16x6 kernel where the geometry allows
+        if (!info) {
+            bool used = false;
+            if (int e = rh_wgrad2d_x6_launch(d, dy, x, dw, workspace, workspace_bytes, stream, &used, dy_range, x_range)) return e;
+            if (used) return RH_OK;
+        } else {
+            long v[12];
+            if (rh_wgrad2d_x6_plan_as_called(d, dy, x, workspace, workspace_bytes, dy_range, x_range, v)) {
+                info[0] = K2_WX6; info[1] = v[0]; info[2] = v[1];
+                info[5] = v[2]; info[6] = v[3]; info[7] = v[4]; info[8] = 0; info[9] = v[5];
+                info[10] = d->c_in < 32 ? d->c_in : 32; info[11] = v[7]; info[12] = v[8]; info[14] = v[6]; info[15] = v[9]; info[16] = v[10];
+                info[18] = 1;
+                return RH_OK;
+            }
+        }
+    }
+    Wgrad2P p;
+    fill_w2(d, &p);
+    p.R = dy; p.Rmul = ymul; p.S = x;
+    const W2Plan w = plan_w2_any(p);
+    const int64_t need = w.Z > 1 ? (int64_t)w.Z * nw * (int64_t)sizeof(float) : 0;
+    if (info) {
+        const Tile2 tl = tile2_of(p.M);
+        info[0] = w.dma ? K2_WDMA : K2_WGRAD;
+        if (w.dma) info[1] = w.tn;
+        else { info[1] = tl.tm; info[2] = tl.tn; info[3] = tl.wm; info[4] = tl.wn; }
+        info[5] = p.rk; info[6] = p.wk; info[7] = w.Z; info[8] = p.chunks_per_z;
+        info[9] = rh_cdiv(p.C * p.T, w.bn) * rh_cdiv(p.M, w.bm);
+        info[10] = p.nc_max; info[11] = (int64_t)w.lds; info[12] = need; info[14] = p.total_chunks; info[15] = p.PH; info[16] = p.PW;
+        info[18] = 0;
+        info[19] = (need == 0 || (workspace && workspace_bytes >= need)) ? 0 : 1;
+        return RH_OK;
+    }
+    RH_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), RH_ERR_WORKSPACE,
+               "conv2d_bwd_weight: workspace %lld B < %lld B", (long long)workspace_bytes, (long long)need);
+    p.out = w.Z > 1 ? (float*)workspace : dw;
+    if (int e = run_w2(p, w, stream)) return e;
+    if (w.Z > 1) return rh_reduce_partials_launch((const float*)workspace, dw, nw, w.Z, stream, "conv2d_bwd_weight_reduce");
+    return RH_OK;
+}
+
+}  // namespace
+
 extern "C" int rh_conv2d_fwd_f32(const rh_conv2d_desc* d, const float* x, const float* wp_fwd, const float* bias,
                                  float* y, rh_stream_t stream) {
     const RhKernelEventsScope events;
@@ -1256,40 +1467,11 @@ extern "C" int rh_conv2d_fwd_f32(const rh_conv2d_desc* d, const float* x, const 
     if (int e = validate2(d)) return e;
     if (d->batch == 0) return RH_OK;
     RH_REQUIRE(x && wp_fwd && y, RH_ERR_INVALID, "conv2d_fwd: null pointer");
+    bool x6 = false;
+    if (int e = route_conv2(d, 0, x, nullptr, wp_fwd, bias, y, in_range, out_range, (hipStream_t)stream, &x6, nullptr)) return e;
     // kernels other than conv2d_x6_kernel do not publish the output's range: a requested slot is filled by a pass over y
-    auto range_after = [&](int e) {
-        return (e || !out_range) ? e : rh_amax_f32(y, (int64_t)d->batch * d->c_out * d->h_out * d->w_out, out_range, stream);
-    };
-    Plan2 t;
-    build_plan2(d, 0, &t);
-    Conv2P p{};
-    fill_common(t, &p, d->c_in, d->c_out);
-    p.in = x; p.wp = wp_fwd; p.out = y; p.bias = bias; p.in_mul = nullptr;
-    p.B = d->batch;
-    p.in_h = d->h_in; p.in_w = d->w_in; p.out_h = d->h_out; p.out_w = d->w_out;
-    p.rows = d->h_out; p.qcols = d->w_out;
-    p.is_h = d->sh; p.is_w = d->sw; p.os_h = 1; p.os_w = 1;
-    p.mul_act = RH_ACT_NONE; p.mul_slope = 0.f;
-    p.epi_act = d->act; p.epi_slope = d->act_slope;
-    if (rh_conv2d_smallm_eligible(d, 0)) return range_after(rh_conv2d_smallm_launch(d, 0, x, wp_fwd, bias, y, (hipStream_t)stream));
-    if (rh_conv2d_smallc_fwd_eligible(d)) return range_after(rh_conv2d_smallc_fwd_launch(d, x, wp_fwd, bias, y, (hipStream_t)stream));
-    {   // exact f32 on the bf16 matrix cores where the geometry allows (C in blocks of 16): conv2d_x6.hip
-        C2X q;
-        fill_c2x(t, d->c_in, d->c_out, wp_fwd, &q);
-        if (q.wq) {
-            q.in = x; q.out = y; q.bias = bias;
-            q.B = d->batch;
-            q.in_h = d->h_in; q.in_w = d->w_in; q.out_h = d->h_out; q.out_w = d->w_out;
-            q.rows = d->h_out; q.qcols = d->w_out;
-            q.is_h = d->sh; q.is_w = d->sw; q.os_h = 1; q.os_w = 1;
-            q.out_act = d->act; q.out_slope = d->act_slope;
-            q.in_range = in_range; q.out_range = out_range;
-            bool used = false;
-            if (int e = rh_conv2d_x6_launch(q, (hipStream_t)stream, "conv2d_fwd_x6", &used)) return e;
-            if (used) return RH_OK;
-        }
-    }
-    return range_after(launch_conv2(p, t, (hipStream_t)stream, "conv2d_fwd"));
+    if (x6 || !out_range) return RH_OK;
+    return rh_amax_f32(y, (int64_t)d->batch * d->c_out * d->h_out * d->w_out, out_range, stream);
 }
 
 extern "C" int rh_conv2d_bwd_data_f32(const rh_conv2d_desc* d, const float* dy, const float* y, const float* wp_bwd,
@@ -1301,40 +1483,11 @@ extern "C" int rh_conv2d_bwd_data_f32(const rh_conv2d_desc* d, const float* dy, 
     if (int e = validate2(d)) return e;
     if (d->batch == 0) return RH_OK;
     RH_REQUIRE(dy && wp_bwd && dx, RH_ERR_INVALID, "conv2d_bwd_data: null pointer");
-    auto range_after = [&](int e) {
-        return (e || !out_range) ? e : rh_amax_f32(dx, (int64_t)d->batch * d->c_in * d->h_in * d->w_in, out_range, stream);
-    };
     RH_REQUIRE(d->act == RH_ACT_NONE || y, RH_ERR_INVALID, "conv2d_bwd_data: the output activation needs y");
-    Plan2 t;
-    build_plan2(d, 1, &t);
-    Conv2P p{};
-    fill_common(t, &p, d->c_out, d->c_in);
-    p.in = dy; p.wp = wp_bwd; p.out = dx; p.bias = nullptr;
-    p.in_mul = d->act == RH_ACT_NONE ? nullptr : y;
-    p.B = d->batch;
-    p.in_h = d->h_out; p.in_w = d->w_out; p.out_h = d->h_in; p.out_w = d->w_in;
-    p.rows = rh_cdiv(d->h_in, d->sh); p.qcols = rh_cdiv(d->w_in, d->sw);
-    p.is_h = 1; p.is_w = 1; p.os_h = d->sh; p.os_w = d->sw;
-    p.mul_act = d->act; p.mul_slope = d->act_slope;
-    p.epi_act = RH_ACT_NONE; p.epi_slope = 0.f;
-    if (rh_conv2d_smallm_eligible(d, 1)) return range_after(rh_conv2d_smallm_launch(d, 1, dy, wp_bwd, nullptr, dx, (hipStream_t)stream));
-    if (d->act == RH_ACT_NONE) {   // (the caller has folded act'(y) into dy: rave_amd.ops._Conv2dFn.backward)
-        C2X q;
-        fill_c2x(t, d->c_out, d->c_in, wp_bwd, &q);
-        if (q.wq) {
-            q.in = dy; q.out = dx; q.bias = nullptr;
-            q.B = d->batch;
-            q.in_h = d->h_out; q.in_w = d->w_out; q.out_h = d->h_in; q.out_w = d->w_in;
-            q.rows = rh_cdiv(d->h_in, d->sh); q.qcols = rh_cdiv(d->w_in, d->sw);
-            q.is_h = 1; q.is_w = 1; q.os_h = d->sh; q.os_w = d->sw;
-            q.out_act = RH_ACT_NONE; q.out_slope = 0.f;
-            q.in_range = in_range; q.out_range = out_range;
-            bool used = false;
-            if (int e = rh_conv2d_x6_launch(q, (hipStream_t)stream, "conv2d_bwd_data_x6", &used)) return e;
-            if (used) return RH_OK;
-        }
-    }
-    return range_after(launch_conv2(p, t, (hipStream_t)stream, "conv2d_bwd_data"));
+    bool x6 = false;
+    if (int e = route_conv2(d, 1, dy, y, wp_bwd, nullptr, dx, in_range, out_range, (hipStream_t)stream, &x6, nullptr)) return e;
+    if (x6 || !out_range) return RH_OK;
+    return rh_amax_f32(dx, (int64_t)d->batch * d->c_in * d->h_in * d->w_in, out_range, stream);
 }
 
 // 1 = the weight gradient of this geometry runs on the bf16 matrix cores (wgrad2d_x6.hip), 0 = f32-input MFMA kernels
@@ -1392,29 +1545,29 @@ extern "C" int rh_conv2d_bwd_weight_f32(const rh_conv2d_desc* d, const float* dy
     }
     workspace = workspace ? (void*)((char*)workspace + bias_ws) : nullptr;
     workspace_bytes = workspace_bytes > bias_ws ? workspace_bytes - bias_ws : 0;
-    if (d->act == RH_ACT_NONE) {      // (the caller has folded act'(y) into dy) -- bf16x6 kernel where the geometry allows
-        bool used = false;
-        if (int e = rh_wgrad2d_x6_launch(d, dy, x, dw, workspace, workspace_bytes, stream, &used, dy_range, x_range)) return e;
-        if (used) return RH_OK;
+    return route_wgrad2(d, dy, ymul, x, dw, workspace, workspace_bytes, dy_range, x_range, stream, nullptr);
+}
+
+extern "C" int rh_conv2d_instance_info(const rh_conv2d_desc* d, int32_t which, int32_t ranges_armed, int32_t data_aligned16,
+                                       int32_t packed_aligned16, int64_t workspace_bytes, int64_t* out) {
+    RH_REQUIRE(out && which >= 0 && which <= 2, RH_ERR_INVALID, "conv2d_instance_info: bad arguments");
+    for (int i = 0; i < kInfo2; ++i) out[i] = 0;
+    out[0] = -1;
+    if (int e = validate2(d)) return e;
+    if (d->batch == 0) return RH_OK;
+    // stand-ins with the stated properties: nothing is launched and nothing dereferenced
+    static const unsigned slot[kRangeSlotWords] = {};
+    static float mem[64] __attribute__((aligned(64)));
+    float* data = mem + (data_aligned16 ? 0 : 1);
+    float* packed = mem + 16 + (packed_aligned16 ? 0 : 1);
+    const unsigned* range = ranges_armed ? slot : nullptr;
+    if (which < 2) {
+        bool x6 = false;
+        return route_conv2(d, which, data, data, packed, nullptr, data, range, nullptr, nullptr, &x6, out);
     }
-    Wgrad2P p;
-    fill_w2(d, &p);
-    p.R = dy; p.Rmul = ymul; p.S = x;
-    W2Plan w{};
-    int tn = 0;
-    const bool dma = plan_w2_dma(p, &w, &tn);
-    if (!dma) w = plan_w2(p);
-    const int64_t need = w.Z > 1 ? (int64_t)w.Z * nw * (int64_t)sizeof(float) : 0;
-    RH_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), RH_ERR_WORKSPACE,
-               "conv2d_bwd_weight: workspace %lld B < %lld B", (long long)workspace_bytes, (long long)need);
-    p.out = w.Z > 1 ? (float*)workspace : dw;
-    int e;
-    if (dma) e = tn == 1 ? launch_w2_dma<1>(p, w, stream) : (tn == 2 ? launch_w2_dma<2>(p, w, stream) : launch_w2_dma<4>(p, w, stream));
-    else if (w.bm == 32) e = launch_w2<1, 2, 1, 4>(p, w, stream);
-    else if (w.bm == 64) e = launch_w2<2, 1, 1, 4>(p, w, stream);
-    else if (w.bm == 96) e = launch_w2<3, 1, 1, 4>(p, w, stream);
-    else e = launch_w2<2, 2, 2, 2>(p, w, stream);
-    if (e) return e;
-    if (w.Z > 1) return rh_reduce_partials_launch((const float*)workspace, dw, nw, w.Z, stream, "conv2d_bwd_weight_reduce");
-    return RH_OK;
+    const int64_t bias_ws = rh_bias_grad_workspace(d->c_out);
+    out[13] = bias_ws;
+    void* ws = workspace_bytes > bias_ws ? (void*)mem : nullptr;
+    return route_wgrad2(d, data, d->act == RH_ACT_NONE ? nullptr : data, data, data, ws, workspace_bytes > bias_ws ? workspace_bytes - bias_ws : 0,
+                        range, range, nullptr, out);
 }

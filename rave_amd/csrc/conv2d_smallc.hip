@@ -146,18 +146,41 @@ bool rh_conv2d_smallc_fwd_eligible(const rh_conv2d_desc* d) {
     return tiles < 0x7fffffffl && lds <= 64 * 1024;
 }
 
-int rh_conv2d_smallc_fwd_launch(const rh_conv2d_desc* d, const float* x, const float* wp_fwd, const float* bias, float* y,
-                                hipStream_t stream) {
-    SmallC2P p{};
-    p.in = x; p.wp = wp_fwd; p.bias = bias; p.out = y;
+namespace {
+
+void plan_smallc(const rh_conv2d_desc* d, SmallC2P* pp, size_t* lds_out, dim3* grid_out) {
+    SmallC2P& p = *pp;
+    p = SmallC2P{};
     p.B = d->batch; p.C = d->c_in; p.M = d->c_out;
     p.in_h = d->h_in; p.in_w = d->w_in; p.out_h = d->h_out; p.out_w = d->w_out;
     p.kw = d->kw; p.dw = d->dw; p.ph = d->ph; p.pw = d->pw;
     p.out_act = d->act; p.out_slope = d->act_slope;
     p.tiles_w = rh_cdiv(p.out_w, kScTW); p.tiles_h = rh_cdiv(p.out_h, kScTH);
     p.PW = kScTW + (d->kw - 1) * d->dw;
-    const size_t lds = (size_t)p.C * (d->kw * d->kh * 32 + (kScTH + d->kh - 1) * p.PW) * 4;
-    const dim3 grid((unsigned)((long)p.B * p.tiles_h * p.tiles_w));
+    *lds_out = (size_t)p.C * (d->kw * d->kh * 32 + (kScTH + d->kh - 1) * p.PW) * 4;
+    *grid_out = dim3((unsigned)((long)p.B * p.tiles_h * p.tiles_w));
+}
+
+}  // namespace
+
+// Diagnostics: {KH, tile rows, tile columns, patch rows, patch pitch, LDS bytes, workgroups, row tiles, column tiles} of the launch
+// of an eligible geometry
+void rh_conv2d_smallc_fwd_plan_info(const rh_conv2d_desc* d, long* out) {
+    SmallC2P p;
+    size_t lds;
+    dim3 grid;
+    plan_smallc(d, &p, &lds, &grid);
+    out[0] = d->kh; out[1] = kScTH; out[2] = kScTW; out[3] = kScTH + d->kh - 1; out[4] = p.PW; out[5] = (long)lds; out[6] = grid.x;
+    out[7] = p.tiles_h; out[8] = p.tiles_w;
+}
+
+int rh_conv2d_smallc_fwd_launch(const rh_conv2d_desc* d, const float* x, const float* wp_fwd, const float* bias, float* y,
+                                hipStream_t stream) {
+    SmallC2P p;
+    size_t lds;
+    dim3 grid;
+    plan_smallc(d, &p, &lds, &grid);
+    p.in = x; p.wp = wp_fwd; p.bias = bias; p.out = y;
     if (d->kh == 9) rh_launch_main(conv2d_smallc_fwd_kernel<9>, grid, dim3(256), lds, stream, p);
     else rh_launch_main(conv2d_smallc_fwd_kernel<3>, grid, dim3(256), lds, stream, p);
     return rh_check_launch("conv2d_smallc_fwd");

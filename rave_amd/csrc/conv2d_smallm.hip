@@ -165,11 +165,12 @@ bool rh_conv2d_smallm_eligible(const rh_conv2d_desc* d, int which) {
     return in_el < (1l << 40) && out_el < (1l << 40) && tiles < 0x7fffffffl && 64 + (d->kw - 1) * d->dw <= 128;
 }
 
-// wp: the f32 section of the packed operand of that direction ([slot = th * kw + tw][c][Mp], Mp = 32)
-int rh_conv2d_smallm_launch(const rh_conv2d_desc* d, int which, const float* in, const float* wp, const float* bias, float* out,
-                            hipStream_t stream) {
-    SmallM2P p{};
-    p.in = in; p.wp = wp; p.bias = which == 0 ? bias : nullptr; p.out = out;
+namespace {
+
+// The launch of a geometry rh_conv2d_smallm_eligible accepts: parameter block (pointers aside), MM, LDS bytes and grid.
+void plan_smallm(const rh_conv2d_desc* d, int which, SmallM2P* pp, int* mm_out, size_t* lds_out, dim3* grid_out) {
+    SmallM2P& p = *pp;
+    p = SmallM2P{};
     p.B = d->batch;
     p.kw = d->kw; p.dw = d->dw;
     if (which == 0) {
@@ -189,9 +190,34 @@ int rh_conv2d_smallm_launch(const rh_conv2d_desc* d, int which, const float* in,
     const int PHt = kSmTH + d->kh - 1;
     p.ck = 4;
     while (p.ck > 1 && (size_t)p.ck * PHt * p.PW * 4 > 48 * 1024) p.ck >>= 1;
-    const int mm = p.M == 1 ? 1 : (p.M == 2 ? 2 : 4);
-    const size_t lds = (size_t)p.ck * (PHt * p.PW + d->kw * d->kh * mm) * 4;
-    const dim3 grid((unsigned)((long)p.B * p.tiles_h * p.tiles_w));
+    *mm_out = p.M == 1 ? 1 : (p.M == 2 ? 2 : 4);
+    *lds_out = (size_t)p.ck * (PHt * p.PW + d->kw * d->kh * *mm_out) * 4;
+    *grid_out = dim3((unsigned)((long)p.B * p.tiles_h * p.tiles_w));
+}
+
+}  // namespace
+
+// Diagnostics: {KH, MM, FLIP, tile rows, tile columns, patch rows, patch pitch, channels per LDS chunk, LDS bytes, workgroups, row
+// tiles, column tiles} of the launch of an eligible geometry
+void rh_conv2d_smallm_plan_info(const rh_conv2d_desc* d, int which, long* out) {
+    SmallM2P p;
+    int mm;
+    size_t lds;
+    dim3 grid;
+    plan_smallm(d, which, &p, &mm, &lds, &grid);
+    out[0] = d->kh; out[1] = mm; out[2] = which ? 1 : 0; out[3] = kSmTH; out[4] = kSmTW; out[5] = kSmTH + d->kh - 1; out[6] = p.PW;
+    out[7] = p.ck; out[8] = (long)lds; out[9] = grid.x; out[10] = p.tiles_h; out[11] = p.tiles_w;
+}
+
+// wp: the f32 section of the packed operand of that direction ([slot = th * kw + tw][c][Mp], Mp = 32)
+int rh_conv2d_smallm_launch(const rh_conv2d_desc* d, int which, const float* in, const float* wp, const float* bias, float* out,
+                            hipStream_t stream) {
+    SmallM2P p;
+    int mm;
+    size_t lds;
+    dim3 grid;
+    plan_smallm(d, which, &p, &mm, &lds, &grid);
+    p.in = in; p.wp = wp; p.bias = which == 0 ? bias : nullptr; p.out = out;
     if (d->kh == 9) { if (which) smallm_go<9, 1>(p, mm, grid, lds, stream); else smallm_go<9, 0>(p, mm, grid, lds, stream); }
     else            { if (which) smallm_go<3, 1>(p, mm, grid, lds, stream); else smallm_go<3, 0>(p, mm, grid, lds, stream); }
     return rh_check_launch(which ? "conv2d_smallm_dgrad" : "conv2d_smallm_fwd");

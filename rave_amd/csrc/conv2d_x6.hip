@@ -367,14 +367,24 @@ long rh_conv2d_x6_units(int C, int M, int nphase, const int* ntaps, long* ph_ofs
     return u;
 }
 
-bool rh_conv2d_x6_plan_query(C2X p, long* out) {
+bool rh_conv2d_x6_plan_as_called(C2X p, long* out) {
     C2XPlan pl{};
-    static const unsigned any_range[kRangeSlotWords] = {};
-    if (!p.in_range) p.in_range = any_range;       // planning only
     if (!plan_c2x(p, &pl)) return false;
     out[0] = pl.tm; out[1] = pl.tn; out[2] = pl.nq; out[3] = p.TR; out[4] = p.TQ; out[5] = p.nb;
     out[6] = (long)pl.lds;
     out[7] = (long)pl.grid.x * pl.grid.y * pl.grid.z;
+    out[8] = p.PH; out[9] = p.PW;
+    out[10] = pl.grid.x; out[11] = pl.grid.y; out[12] = pl.grid.z;
+    out[13] = p.tiles_r; out[14] = p.tiles_q;
+    return true;
+}
+
+bool rh_conv2d_x6_plan_query(C2X p, long* out) {
+    static const unsigned any_range[kRangeSlotWords] = {};
+    if (!p.in_range) p.in_range = any_range;       // planning only
+    long v[15];
+    if (!rh_conv2d_x6_plan_as_called(p, v)) return false;
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
     return true;
 }
 

@@ -42,3 +42,7 @@ long rh_conv2d_x6_units(int C, int M, int nphase, const int* ntaps, long* ph_ofs
 int rh_conv2d_x6_launch(C2X& p, hipStream_t stream, const char* what, bool* used);
 // Diagnostics: {tm, tn, nq, TR, TQ, nb, lds bytes, workgroups}; false = not eligible
 bool rh_conv2d_x6_plan_query(C2X p, long* out8);
+// The plan rh_conv2d_x6_launch would make for exactly this parameter block (range slot and pointers as given, nothing assumed):
+// {tm, tn, nq, TR, TQ, nb, lds bytes, workgroups, PH, PW, grid x, grid y, grid z, row tiles, column tiles}; false = that launch
+// would leave the call to the f32-input kernels
+bool rh_conv2d_x6_plan_as_called(C2X p, long* out15);

@@ -373,6 +373,37 @@ int64_t rh_wgrad2d_x6_workspace(const rh_conv2d_desc* d) {
     return (int64_t)pl.Z * d->c_out * d->c_in * d->kh * d->kw * (int64_t)sizeof(float);
 }
 
+namespace {
+
+// The whole decision of a call: the plan, and whether the range slots, the pointers and the scratch offered let it run.
+bool select_w2x(const rh_conv2d_desc* d, const float* dy, const float* x, const void* ws, int64_t ws_bytes, const unsigned* dy_range,
+                const unsigned* x_range, W2X* p, W2XPlan* pl) {
+    if (RH_X6_F16 && (!dy_range || !x_range)) return false;      // no range slots (rh_x6_set_ranges): f32-input MFMA kernels
+    if (!plan_w2x(d, p, pl)) return false;
+    const int64_t need = (int64_t)pl->Z * d->c_out * d->c_in * d->kh * d->kw * (int64_t)sizeof(float);
+    if (((uintptr_t)dy & 3) || ((uintptr_t)x & 3)) return false;
+    if (pl->Z > 1 && (!ws || ws_bytes < need)) return false;
+    return true;
+}
+
+}  // namespace
+
+// Diagnostics: what rh_wgrad2d_x6_launch would do with exactly these arguments (nothing is launched).  out12 = {NQX, SW, TR, TQ, Z,
+// channel groups, tiles, LDS bytes, scratch bytes used (0 when Z == 1), PH, plane pitch, conversion tasks of the fullest group};
+// false = that call leaves the gradient to the f32-input kernels.
+bool rh_wgrad2d_x6_plan_as_called(const rh_conv2d_desc* d, const float* dy, const float* x, const void* ws, int64_t ws_bytes,
+                                  const unsigned* dy_range, const unsigned* x_range, long* out) {
+    W2X p;
+    W2XPlan pl{};
+    if (!select_w2x(d, dy, x, ws, ws_bytes, dy_range, x_range, &p, &pl)) return false;
+    out[0] = d->sw == 2 ? 3 : pl.nqx; out[1] = d->sw;
+    out[2] = p.TR; out[3] = p.TQ; out[4] = pl.Z; out[5] = pl.groups; out[6] = p.tiles_total;
+    out[7] = (long)pl.lds;
+    out[8] = pl.Z > 1 ? (long)pl.Z * d->c_out * d->c_in * d->kh * d->kw * (long)sizeof(float) : 0;
+    out[9] = p.PH; out[10] = p.PWp; out[11] = p.nxt;
+    return true;
+}
+
 // dw = sum over positions of dy (x) x-patches; dy already carries act'(y).  *used = false when the geometry (or the scratch
 // offered) does not fit.
 int rh_wgrad2d_x6_launch(const rh_conv2d_desc* d, const float* dy, const float* x, float* dw, void* ws, int64_t ws_bytes,
@@ -380,13 +411,9 @@ int rh_wgrad2d_x6_launch(const rh_conv2d_desc* d, const float* dy, const float* 
     *used = false;
     W2X p;
     W2XPlan pl{};
-    if (RH_X6_F16 && (!dy_range || !x_range)) return RH_OK;      // no range slots (rh_x6_set_ranges): f32-input MFMA kernels
-    if (!plan_w2x(d, &p, &pl)) return RH_OK;
+    if (!select_w2x(d, dy, x, ws, ws_bytes, dy_range, x_range, &p, &pl)) return RH_OK;
     p.g_range = dy_range; p.x_range = x_range;
     const long nw = (long)d->c_out * d->c_in * d->kh * d->kw;
-    const int64_t need = (int64_t)pl.Z * nw * (int64_t)sizeof(float);
-    if (((uintptr_t)dy & 3) || ((uintptr_t)x & 3)) return RH_OK;
-    if (pl.Z > 1 && (!ws || ws_bytes < need)) return RH_OK;
     p.G = dy; p.X = x;
     p.out = pl.Z > 1 ? (float*)ws : dw;
     if (d->sw == 2) w2x_go<3, 2>(p, pl, stream);

@@ -722,6 +722,8 @@ def test_v2_full_size_forward_vs_oracle(dev, batch):
 
 
 # --------------------------------------------------------------------------- general Conv2d
+# Layer-sized geometries through autograd, whole tensors.  Which kernel INSTANCE runs, and the tile edges, are pinned by
+# tests/conv2d_matrix.py (tests/test_conv2d_matrix_host.py, tests/test_gpu_conv2d_matrix.py).
 # (B, Ci, Co, H, W, (kh,kw), (sh,sw), (dh,dw), (ph,pw), act)
 CONV2D_CASES = [
     (2, 2, 8, 257, 29, (9, 3), (1, 1), (1, 1), (4, 1), 1),      # Encodec block 0 (rave/discriminator.py:60)
