@@ -32,6 +32,16 @@ inline void rh_launch_main(K kern, dim3 grid, dim3 block, size_t lds, hipStream_
         hipLaunchKernelGGL(kern, grid, block, lds, stream, args...);
     }
 }
+// Launch of a kernel whose dynamic LDS may exceed the 64 KiB default: raises its limit to the CU's 160 KiB once (Kern is a
+// template argument, so every kernel instance has its own flag), then launches -- MAIN: as rh_launch_main does.
+template <auto Kern, bool MAIN = false, typename... A>
+inline void rh_launch_big_lds(dim3 grid, dim3 block, size_t lds, hipStream_t stream, A... args) {
+    static const hipError_t raised =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)raised;
+    if (MAIN) rh_launch_main(Kern, grid, block, lds, stream, args...);
+    else hipLaunchKernelGGL(Kern, grid, block, lds, stream, args...);
+}
 #endif
 
 // consumes the thread's pending range slots (rh_x6_set_ranges): every conv entry point takes them exactly once

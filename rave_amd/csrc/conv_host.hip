@@ -225,22 +225,6 @@ __host__ __device__ __forceinline__ long pack_tiles(const PackP& q) {
 
 // The kX6P pieces of 8 K values as 16-byte fragments.  f16 build: the values are scaled by `sc` (the power of two that takes
 // the tensor's max |w| into [2^14, 2^15): common.hpp) and split hi / lo; bf16 build: exact 3-way truncation split, sc unused.
-__device__ __forceinline__ void emit_fragment_bf3(const float (&v)[8], unsigned* dst, long piece_stride_u32) {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    unsigned h[3][8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        rh_bf3_split(v[i], h[0][i], h[1][i], h[2][i]);
-        h[0][i] &= 0xffff0000u; h[1][i] &= 0xffff0000u; h[2][i] &= 0xffff0000u;
-    }
-#pragma unroll
-    for (int s3 = 0; s3 < 3; ++s3) {
-        u32x4 pk;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) pk[k] = (h[s3][2 * k] >> 16) | h[s3][2 * k + 1];
-        *reinterpret_cast<u32x4*>(dst + s3 * piece_stride_u32) = pk;
-    }
-}
 __device__ __forceinline__ void emit_fragment(const float (&v)[8], unsigned* dst, long piece_stride_u32, float sc) {
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #if RH_X6_F16
@@ -279,7 +263,7 @@ __device__ __forceinline__ void pack_tile(const PackP& q, long tile, float* lds 
     const int tid = threadIdx.x;
     float fsc = 1.f;              // f16 build: scale of the pieces, from the range record the range kernel left behind the fragments
 #if RH_X6_F16
-    if (q.wq && !q.bf16x3) {
+    if (q.wq) {
         int inv;
         fsc = __uint_as_float(rh_x6_scale_bits(q.range[0], &inv));
     }
@@ -336,11 +320,6 @@ __device__ __forceinline__ void pack_tile(const PackP& q, long tile, float* lds 
 #pragma unroll
                 for (int i = 0; i < 8; ++i) v[i] = lds[(sl * 32 + oct * 8 + i) * 33 + ml];
                 const int slot = s0 + sl;
-                if (q.bf16x3) {          // (the 2-D kernels' operand: q2a / q2n were filled for three pieces)
-                    const long unit3 = (long)q.q2a[slot] + (long)(cb >> 4) * q.q2n[slot] + (long)(((cb >> 3) & 1) * 3) * q.Mp + m0 + ml;
-                    emit_fragment_bf3(v, q.wq + unit3 * 4, (long)q.Mp * 4);
-                    continue;
-                }
                 const long unit = (long)q.q2a[slot] + (long)(cb >> 4) * q.q2n[slot] + (long)(((cb >> 3) & 1) * kX6P) * q.Mp + m0 + ml;
                 emit_fragment(v, q.wq + unit * 4, (long)q.Mp * 4, fsc);
             }

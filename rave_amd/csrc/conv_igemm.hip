@@ -10,8 +10,8 @@
 // 16-byte staging), B = input tile [c][position] staged once per channel chunk and re-read for
 // every tap (the im2col matrix is never materialised).  Exact f32: results are k-ordered fmaf
 // chains, same numerics class as the reference's CPU path.
-#include <mutex>
 #include "conv_params.hpp"
+#include "f32_tile.hpp"
 
 namespace {
 
@@ -188,25 +188,12 @@ int launch_cfg(ConvP& p, hipStream_t stream, const char* what) {
         p.pitch = ((bnl - 1) / p.inner + 1) * p.is * p.inner + p.inner + span * p.inner + 1;
     p.pitch |= 1;  // odd pitch: the two k-halves of a wave never share a bank row start
     const int budget = 15 * 1024;  // floats (60 KiB -> two workgroups per CU)
-    const int per_ch = (maxtaps > 0 ? maxtaps : 1) * BM + p.nb * p.pitch;
-    int ck = budget / per_ch;
-    ck &= ~1;
-    if (ck > 32) ck = 32;
-    if (ck < 2) ck = 2;
-    const int cmax = (p.C + 1) & ~1;
-    if (ck > cmax) ck = cmax;
-    p.ck = ck;
+    const int ck = p.ck = ck_for(budget, (maxtaps > 0 ? maxtaps : 1) * BM + p.nb * p.pitch, p.C, false);
     p.wlds_floats = (maxtaps > 0 ? maxtaps : 1) * ck * BM;
     const size_t lds = sizeof(float) * ((size_t)p.wlds_floats + (size_t)p.nb * ck * p.pitch);
     RH_REQUIRE(lds <= 160 * 1024, RH_ERR_UNSUPPORTED, "%s: tile needs %zu B of LDS", what, lds);
-    auto kern = conv_igemm_kernel<TM, TN, WM, WN>;
-    static std::once_flag once;
-    std::call_once(once, [&] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
     dim3 grid(rh_cdiv(p.B, p.nb) * p.tiles_per_b, rh_cdiv(p.M, BM), p.nphase);
-    hipLaunchKernelGGL(kern, grid, dim3(WM * WN * 64), lds, stream, p);
+    rh_launch_big_lds<conv_igemm_kernel<TM, TN, WM, WN>>(grid, dim3(WM * WN * 64), lds, stream, p);
     return rh_check_launch(what);
 }
 

@@ -10,13 +10,10 @@
 // register-staged kernel of conv_igemm.hip.  Same math, same accumulation order per output as the
 // synchronous kernel: exact f32, k-ordered fmaf chains.
 #include <cstdlib>
-#include <mutex>
-#include <type_traits>
 #include "conv_params.hpp"
+#include "f32_tile.hpp"
 
 namespace {
-
-typedef __attribute__((address_space(3))) void lds_void;
 
 #ifndef RH_READS_FIRST
 #define RH_READS_FIRST 1
@@ -33,9 +30,8 @@ __device__ __forceinline__ int oidx_of(int n, int inner, int os, int oph) {
     const int r = n / inner;
     return (r * os + oph) * inner + (n - r * inner);
 }
-__device__ __forceinline__ unsigned mdiv(unsigned n, unsigned magic) { return (n * magic) >> 20; }
-
-constexpr unsigned kOOB = 0x80000000u;  // >= any descriptor size we accept -> DMA writes zeros
+// n / d for n * d < 2^20 with magic = magic_of(d) = ceil(2^20 / d) (ConvP keeps 20-bit reciprocals: not f32_tile.hpp's mdiv)
+__device__ __forceinline__ unsigned mdiv20(unsigned n, unsigned magic) { return (n * magic) >> 20; }
 
 template <int TM, int TN, int WM, int WN, bool LEAKY, bool VEC, bool CTAIL>
 __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_dma_kernel(const ConvP p) {
@@ -117,9 +113,9 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_dma_kernel(const ConvP
 #pragma unroll
         for (int i = 0; i < kNX; ++i) {
             const unsigned g = (unsigned)(wave + NW * i) * 64u + lane;
-            const unsigned row = mdiv(g, p.magic_lpr);
+            const unsigned row = mdiv20(g, p.magic_lpr);
             const unsigned v = g - row * lpr;
-            const unsigned bl = mdiv(row, p.magic_ck);
+            const unsigned bl = mdiv20(row, p.magic_ck);
             const unsigned c = row - bl * p.ck;
             const bool ok = row < (unsigned)xrows && b0 + bl < (unsigned)p.B;
             xo[i] = ok ? (bl * p.C + c) * (unsigned)p.in_row + 4u * v : kOOB;
@@ -130,7 +126,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_dma_kernel(const ConvP
             const unsigned f = ((unsigned)(wave + NW * i) * 64u + lane) * 4u;
             const unsigned kr = f / (unsigned)BM;
             const unsigned col = f - kr * BM;
-            const unsigned t = mdiv(kr, p.magic_ck);
+            const unsigned t = mdiv20(kr, p.magic_ck);
             const unsigned c = kr - t * p.ck;
             const bool ok = kr < (unsigned)wrows && m0 + col < (unsigned)p.Mp;
             wo[i] = ok ? (t * p.C + c) * p.Mp + m0 + col : kOOB;
@@ -180,7 +176,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_dma_kernel(const ConvP
             const unsigned f = (unsigned)q * 256u + (unsigned)lane * 4u;
             const unsigned kr = f / (unsigned)BM;
             const unsigned col = f - kr * BM;
-            const unsigned t = mdiv(kr, p.magic_ck);
+            const unsigned t = mdiv20(kr, p.magic_ck);
             const unsigned c = kr - t * p.ck;
             const unsigned ch = c0 + c, m = m0 + col;
             unsigned off = kOOB;
@@ -191,7 +187,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_dma_kernel(const ConvP
         // input tile: rows (batch item, channel), 64-float segments
         float* xs = stage + p.wlds_floats;
         for (int row = wave; row < xrows; row += NW) {
-            const unsigned bl = mdiv((unsigned)row, p.magic_ck);
+            const unsigned bl = mdiv20((unsigned)row, p.magic_ck);
             const unsigned c = row - bl * p.ck;
             const unsigned b = b0 + bl, ch = c0 + c;
             const bool rv = b < (unsigned)p.B && ch < (unsigned)p.C;
@@ -502,26 +498,18 @@ int launch_dma(ConvP& p, hipStream_t stream, const char* what, void* ws, int64_t
     p.ksplit = pl.ksplit;
     p.chunks_per_split = pl.chunks_per_split;
     p.part = (float*)ws;
-    auto launch = [&](auto kern) {
-        dim3 grid(col_tiles, rh_cdiv(p.M, BM), p.nphase * p.ksplit);
-        rh_launch_main(kern, grid, dim3(WM * WN * 64), lds, stream, p);
-    };
-    auto go = [&](auto kern) {
-        static std::once_flag once;
-        std::call_once(once, [&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-        launch(kern);
-    };
+    const dim3 grid(col_tiles, rh_cdiv(p.M, BM), p.nphase * p.ksplit), block(WM * WN * 64);
     const bool leaky = p.in_act == RH_ACT_LEAKY;
     const bool ctail = (p.C % p.ck) != 0;
     if (vec && !ctail) {
-        if (leaky) go(conv_igemm_dma_kernel<TM, TN, WM, WN, true, true, false>);
-        else go(conv_igemm_dma_kernel<TM, TN, WM, WN, false, true, false>);
+        if (leaky) rh_launch_big_lds<conv_igemm_dma_kernel<TM, TN, WM, WN, true, true, false>, true>(grid, block, lds, stream, p);
+        else rh_launch_big_lds<conv_igemm_dma_kernel<TM, TN, WM, WN, false, true, false>, true>(grid, block, lds, stream, p);
     } else if (vec) {
-        if (leaky) go(conv_igemm_dma_kernel<TM, TN, WM, WN, true, true, true>);
-        else go(conv_igemm_dma_kernel<TM, TN, WM, WN, false, true, true>);
+        if (leaky) rh_launch_big_lds<conv_igemm_dma_kernel<TM, TN, WM, WN, true, true, true>, true>(grid, block, lds, stream, p);
+        else rh_launch_big_lds<conv_igemm_dma_kernel<TM, TN, WM, WN, false, true, true>, true>(grid, block, lds, stream, p);
     } else {
-        if (leaky) go(conv_igemm_dma_kernel<TM, TN, WM, WN, true, false, true>);
-        else go(conv_igemm_dma_kernel<TM, TN, WM, WN, false, false, true>);
+        if (leaky) rh_launch_big_lds<conv_igemm_dma_kernel<TM, TN, WM, WN, true, false, true>, true>(grid, block, lds, stream, p);
+        else rh_launch_big_lds<conv_igemm_dma_kernel<TM, TN, WM, WN, false, false, true>, true>(grid, block, lds, stream, p);
     }
     if (int e = rh_check_launch(what)) return e;
     if (p.ksplit > 1) return finalize_launch(p, stream);

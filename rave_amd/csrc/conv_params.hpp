@@ -118,8 +118,6 @@ struct PackP {
     int x6_mode;          // 0 none; 1: step = (16-channel chunk, tap); IS > 1: step = (16/IS-channel chunk, tap group u),
                           //   k slot kappa of the block <-> channel kappa / IS, source tap u*IS + kappa % IS
     int x6_nu;            // IS > 1: tap groups per chunk = ceil(k / IS)
-    int bf16x3;           // 1: the mode-1 section holds THREE bf16 truncation pieces per value whatever the build (the 2-D
-                          //   kernels' operand: conv2d.hip, conv2d_x6.hip), no range record
     // x6_vs = s > 1: a second section ("virtual rows") at fragment x6_vofs: step = (16-channel chunk, tap u < x6_U),
     // row r = m * s + q2j[slot], rows padded to x6_Mvp, fragment of slot = x6_vofs + vq2a[slot] + chunk * x6_U*6*x6_Mvp;
     // (j, u) pairs no slot covers are written as zeros

@@ -8,8 +8,8 @@
 // caller-provided scratch and an ordered second pass -> bitwise deterministic.
 #include <atomic>
 #include <cstdlib>
-#include <mutex>
 #include "conv_params.hpp"
+#include "f32_tile.hpp"
 
 namespace {
 
@@ -335,11 +335,6 @@ __global__ __launch_bounds__(64) void bias_grad2d_finalize_kernel(const float* _
 }
 
 
-typedef __attribute__((address_space(3))) void lds_void;
-constexpr unsigned kOOB = 0x80000000u;
-// exact n / d for n < 2^32 / d with magic = ceil(2^32 / d) (d >= 2); magic == 0 encodes d == 1
-__device__ __forceinline__ unsigned mdiv(unsigned n, unsigned magic) { return magic ? __umulhi(n, magic) : n; }
-
 // Same GEMM as wgrad_kernel, software-pipelined with LDS-DMA: two LDS stages, the DMA engine
 // fills stage (i+1)&1 with the next (batch, position-chunk) tiles of R and S while the matrix
 // cores reduce stage i&1.  Tiles are copied as FLAT arrays (every DMA lane derives its own source
@@ -652,8 +647,6 @@ WPlan plan(const WgradP& p) {
     return w;
 }
 
-inline unsigned magic_of(int d) { return d <= 1 ? 0u : (unsigned)(((1ull << 32) + d - 1) / (unsigned long long)d); }
-
 // The five tile shapes <TM, TN, WM, WN> of the two kernels, by the plan's workgroup tile (rh_wgrad_run instantiates exactly these).
 struct WShape { int tm, tn, wm, wn; };
 WShape w_shape(const WPlan& w) {
@@ -701,14 +694,14 @@ WInst w_configure(WgradP& p, const WPlan& w, const WShape& sh) {
                 p.ps = s_width | 1;
                 p.pr = (w.rk * p.inner) | 1;
             }
-            p.magic_pr = magic_of(p.pr);
-            p.magic_lpr_r = magic_of(p.pr >> 2);
-            p.magic_lpr_s = magic_of(p.ps >> 2);
+            p.magic_pr = magic32(p.pr);
+            p.magic_lpr_r = magic32(p.pr >> 2);
+            p.magic_lpr_s = magic32(p.ps >> 2);
             p.r_floats = (BM * p.pr + 255) & ~255;
             p.s_floats = (p.nc_max * p.ps + 255) & ~255;
             p.stage_floats = p.r_floats + p.s_floats;
-            p.magic_ps = magic_of(p.ps);
-            p.magic_cpb = magic_of(w.chunks_per_b);
+            p.magic_ps = magic32(p.ps);
+            p.magic_cpb = magic32(w.chunks_per_b);
             p.r_bytes = (unsigned)rb;
             p.s_bytes = (unsigned)sbytes;
             const size_t lds = sizeof(float) * 2 * (size_t)p.stage_floats;
@@ -728,27 +721,15 @@ template <int TM, int TN, int WM, int WN>
 int launch_w(WgradP& p, const WPlan& w, hipStream_t stream) {
     const WInst in = w_configure(p, w, WShape{TM, TN, WM, WN});
     const size_t lds = in.lds;
+    const dim3 grid(w.ct, w.mt, w.Z), block(WM * WN * 64);
     if (in.dma) {
-        dim3 grid(w.ct, w.mt, w.Z);
-        auto go = [&](auto kern) {
-            static std::once_flag once;
-            std::call_once(once, [&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-            rh_launch_main(kern, grid, dim3(WM * WN * 64), lds, stream, p);
-        };
-        if (in.leaky == 1) go(wgrad_dma_kernel<TM, TN, WM, WN, true, false>);
-        else if (in.leaky == 2) go(wgrad_dma_kernel<TM, TN, WM, WN, false, true>);
-        else go(wgrad_dma_kernel<TM, TN, WM, WN, false, false>);
+        if (in.leaky == 1) rh_launch_big_lds<wgrad_dma_kernel<TM, TN, WM, WN, true, false>, true>(grid, block, lds, stream, p);
+        else if (in.leaky == 2) rh_launch_big_lds<wgrad_dma_kernel<TM, TN, WM, WN, false, true>, true>(grid, block, lds, stream, p);
+        else rh_launch_big_lds<wgrad_dma_kernel<TM, TN, WM, WN, false, false>, true>(grid, block, lds, stream, p);
         return rh_check_launch("conv1d_bwd_weight(dma)");
     }
     RH_REQUIRE(lds <= 160 * 1024, RH_ERR_UNSUPPORTED, "conv1d_bwd_weight: tile needs %zu B of LDS", lds);
-    auto kern = wgrad_kernel<TM, TN, WM, WN>;
-    static std::once_flag once;
-    std::call_once(once, [&] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
-    dim3 grid(w.ct, w.mt, w.Z);
-    rh_launch_main(kern, grid, dim3(WM * WN * 64), lds, stream, p);
+    rh_launch_big_lds<wgrad_kernel<TM, TN, WM, WN>, true>(grid, block, lds, stream, p);
     return rh_check_launch("conv1d_bwd_weight");
 }
 

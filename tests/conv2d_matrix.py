@@ -35,7 +35,7 @@ PER_CALL = ("RH_CONV2D_X6", "RH_CONV2D_SMALLM", "RH_CONV_X6", "RH_WGRAD2D_X6")
 ONCE_PER_PROCESS = ("RH_CONV2D_X6_TN", "RH_CONV2D_STAGE_FLOATS", "RH_CONV2D_DMA_STAGE_FLOATS", "RH_WGRAD2D_DMA_STAGE_FLOATS",
                     "RH_WGRAD2D_LDS_BYTES", "RH_WGRAD2D_X6_SLICES", "RH_CONV2D_NODMA", "RH_WGRAD2D_NODMA")
 KERNELS = ("x6", "dma", "igemm", "smallm", "smallc", "wx6", "wdma", "wgrad")       # rh_conv2d_instance_info: out[0]
-F0_TILES = ((1, 2, 1, 4), (2, 1, 1, 4), (3, 1, 1, 4), (2, 2, 2, 2))                # conv2d.hip: tile2_of
+F0_TILES = ((1, 2, 1, 4), (2, 1, 1, 4), (3, 1, 1, 4), (2, 2, 2, 2))                # conv2d_f32.hip: tile2_of
 X6_TILES = ((1, 2, 4), (1, 2, 8), (1, 1, 4), (1, 1, 8), (2, 2, 4), (2, 2, 8), (2, 1, 4), (2, 1, 8), (3, 1, 4), (3, 1, 8))
 MAX_B, MAX_CH, MAX_NUMEL = 5, 160, 1 << 19
 
@@ -294,7 +294,7 @@ def edges(row, info):
     return e
 
 
-NO_DMA = ("", "fused derivative", "2 GB", "patch too large", "LDS", "grid", "switched off")     # conv2d.hip: plan2_dma
+NO_DMA = ("", "fused derivative", "2 GB", "patch too large", "LDS", "grid", "switched off")     # conv2d_f32.hip: plan2_dma
 
 GEOMETRY = ["partial last row tile", "partial last column tile", "nb > 1, B % nb != 0", "M % row tile != 0", "M = 1 in a 32-row tile",
             "four paddings", "no padding", "dilation in H", "dilation in W", "dilation in both", "stride in H", "stride in W", "stride in both",

@@ -58,16 +58,16 @@ def test_rows_are_small():
 
 def test_the_inventory_is_the_code():
     """The instance lists of conv2d_matrix are what the sources instantiate."""
-    src = {n: open(os.path.join(CSRC, n)).read() for n in ("conv2d_x6.hip", "conv2d.hip", "wgrad2d_x6.hip", "conv2d_smallm.hip",
+    src = {n: open(os.path.join(CSRC, n)).read() for n in ("conv2d_x6.hip", "conv2d_f32.hip", "wgrad2d_x6.hip", "conv2d_smallm.hip",
                                                            "conv2d_smallc.hip")}
     # conv2d_x6.hip: the RH_C2X_CASE list, less the case of the bf16 comparison build (#if !RH_X6_F16)
     x6 = re.sub(r"#if !RH_X6_F16.*?#endif", "", src["conv2d_x6.hip"], flags=re.S)
     cases = {tuple(map(int, m)) for m in re.findall(r"RH_C2X_CASE\((\d), (\d), (\d)\)", x6)}
     assert cases == set(M.X6_TILES) and len(cases) == 10
-    tiles = {tuple(map(int, m)) for m in re.findall(r"go2<(\d), (\d), (\d), (\d)>", src["conv2d.hip"])}
-    assert tiles == {tuple(map(int, m)) for m in re.findall(r"launch_w2<(\d), (\d), (\d), (\d)>", src["conv2d.hip"])} == set(M.F0_TILES)
-    assert set(re.findall(r"launch_w2_dma<(\d)>\(p", src["conv2d.hip"])) == {"1", "2", "4"}
-    assert len(M.NO_DMA) == len(re.search(r"enum \{ kDma = 0,([^}]*)\}", src["conv2d.hip"]).group(1).split(",")) + 1
+    tiles = {tuple(map(int, m)) for m in re.findall(r"go2<(\d), (\d), (\d), (\d)>", src["conv2d_f32.hip"])}
+    assert tiles == {tuple(map(int, m)) for m in re.findall(r"launch_w2<(\d), (\d), (\d), (\d)>", src["conv2d_f32.hip"])} == set(M.F0_TILES)
+    assert set(re.findall(r"launch_w2_dma<(\d)>\(p", src["conv2d_f32.hip"])) == {"1", "2", "4"}
+    assert len(M.NO_DMA) == len(re.search(r"enum \{ kDma = 0,([^}]*)\}", src["conv2d_f32.hip"]).group(1).split(",")) + 1
     assert set(re.findall(r"w2x_go<(\d), (\d)>", src["wgrad2d_x6.hip"])) == {("3", "2"), ("3", "1"), ("6", "1")}
     assert set(re.findall(r"smallm_go<(\d), (\d)>", src["conv2d_smallm.hip"])) == {("9", "1"), ("9", "0"), ("3", "1"), ("3", "0")}
     assert set(re.findall(r"conv2d_smallm_kernel<KH, (\d), FLIP>", src["conv2d_smallm.hip"])) == {"1", "2", "4"}
