@@ -483,6 +483,28 @@ int rh_feed_batch_pitch_i16_f32(const int16_t* pcm, int64_t pcm_samples, const r
                                 const rh_feed_pitch_row* rows_dev, const double* taps, int32_t n_taps, const float* noise,
                                 int32_t n_rows, int32_t n_signal, int32_t bit_depth, float* out, rh_stream_t stream);
 
+/* The chain of rh_feed_batch_pitch_i16_f32 with the two steps `rave train --normalize` / `--derivative` put between
+ * Dequantize and the augmentations (scripts/train.py:61-63,160-167, rave/dataset.py:241-245).  With v[r][i] = y[i] +
+ * noise[r][i] / 2^bit_depth in float64 (the value the pitched entry point rounds to float32), rows r of one item being
+ * n_channels consecutive rows:
+ *   normalize  != 0: peak = max |v| over ALL rows and samples of the item (normalize_signal, rave/dataset.py:196-204);
+ *                    gain = 1 if peak == 0, else 10^(min(max_gain_db, -20 log10(peak)) / 20);  otherwise gain = 1
+ *   derivative != 0: out[r][i] = float32(0.5 v[r][i] gain - 0.5 v[r][i - 1] gain), v[r][-1] = 0   (lfilter([.5, -.5], [1], .)
+ *                    in float64, rave/dataset.py:24-29);  otherwise out[r][i] = float32(v[r][i] gain)
+ * all in float64 with ONE rounding to float32 at the end; a row with mute != 0 is all zeros and adds nothing to the peak.
+ * Two launches on `stream`: the chain kernel leaves v and one peak per row in `workspace` (rh_feed_post_workspace_bytes
+ * bytes, 8-byte aligned device memory owned by the caller, free for reuse once the call's work on the stream is done), the
+ * second applies gain, difference and rounding; the peaks are reduced by max in a fixed order, the result is the same bits
+ * on every run.  normalize == 0 && derivative == 0 is rh_feed_batch_pitch_i16_f32 (same bits; workspace may be NULL).
+ * Checked on the host, RH_ERR_INVALID and no launch otherwise: everything rh_feed_batch_pitch_i16_f32 checks,
+ * n_rows % n_channels == 0, max_gain_db finite, the size and alignment of the workspace. */
+int64_t rh_feed_post_workspace_bytes(int32_t n_rows, int32_t n_signal);
+int rh_feed_batch_post_i16_f32(const int16_t* pcm, int64_t pcm_samples, const rh_feed_pitch_row* rows,
+                               const rh_feed_pitch_row* rows_dev, const double* taps, int32_t n_taps, const float* noise,
+                               int32_t n_rows, int32_t n_signal, int32_t bit_depth, int32_t n_channels, int32_t normalize,
+                               double max_gain_db, int32_t derivative, void* workspace, int64_t workspace_bytes, float* out,
+                               rh_stream_t stream);
+
 /* ---- spectral distance ("next" item #1 of SURVEY.md section 8f, beside the hot path) ------------- */
 
 /* STFT framing of torchaudio.transforms.Spectrogram(center=True, pad_mode="reflect") as used by

@@ -11,6 +11,8 @@
 // store.  The recurrence is sequential by nature (0.5 ms for 65536 samples) but rows run in parallel and the
 // kernel is meant for a side stream, under the training step.
 #include <algorithm>
+#include <cmath>
+#include <cstdint>
 #include "common.hpp"
 
 namespace {
@@ -71,19 +73,28 @@ __host__ __device__ inline int feed_gcd(int a, int b) {
 }
 __host__ __device__ inline int feed_tap_stride(int up, int H) { return ((2 * H + up) / up) | 1; }
 
+// kPost (normalize / derivative behind Dequantize, feed_post_kernel below): the row is not rounded and stored to `out` but kept
+// in float64 in `ws` (rows x n_signal), and max |row| goes to peaks[r]; a muted row only reports the peak 0.
+template <bool kPost>
 __global__ __launch_bounds__(256) void feed_pitch_kernel(const int16_t* __restrict__ pcm, const rh_feed_pitch_row* __restrict__ rows,
                                                          const double* __restrict__ taps, const float* __restrict__ noise,
-                                                         int n_signal, double quant, float* __restrict__ out) {
+                                                         int n_signal, double quant, float* __restrict__ out,
+                                                         double* __restrict__ ws, double* __restrict__ peaks) {
     __shared__ double buf[kChunk];
     __shared__ double hp[kTapSlots];
     __shared__ float span[kSpan];
     const int r = blockIdx.x;
     const rh_feed_pitch_row row = rows[r];
     if (row.mute) {                             // (x + noise) * 0
-        for (int i = threadIdx.x; i < n_signal; i += 256) out[(long)r * n_signal + i] = 0.f;
+        if constexpr (kPost) {
+            if (threadIdx.x == 0) peaks[r] = 0.0;
+        } else {
+            for (int i = threadIdx.x; i < n_signal; i += 256) out[(long)r * n_signal + i] = 0.f;
+        }
         return;
     }
-    const int g = feed_gcd(row.up, row.down);
+    [[maybe_unused]] double peak = 0.0;
+    const int g =feed_gcd(row.up, row.down);
     const int up = row.up / g, down = row.down / g;
     const bool pitched = up != down;
     const int H = 10 * max(up, down);
@@ -142,10 +153,97 @@ __global__ __launch_bounds__(256) void feed_pitch_kernel(const int16_t* __restri
         __syncthreads();
         for (int i = threadIdx.x; i < len; i += 256) {
             const long o = (long)r * n_signal + c0 + i;
-            out[o] = (float)(buf[i] + (double)noise[o] * quant);
+            const double v = buf[i] + (double)noise[o] * quant;
+            if constexpr (kPost) {
+                ws[o] = v;
+                peak = fmax(peak, fabs(v));
+            } else {
+                out[o] = (float)v;
+            }
         }
         __syncthreads();
     }
+    if constexpr (kPost) {                      // max is exact: any reduction order gives the same bits
+        buf[threadIdx.x] = peak;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if ((int)threadIdx.x < s) buf[threadIdx.x] = fmax(buf[threadIdx.x], buf[threadIdx.x + s]);
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) peaks[r] = buf[0];
+    }
+}
+
+// ---- normalize_signal and the derivator behind Dequantize (`rave train --normalize / --derivative`) ---------------------
+//   normalize_signal(x, max_gain_db)  (dataset.py:196-204,241-242: peak = max |x| over the WHOLE item, every channel;
+//                                      peak == 0 -> x, else x * 10^(min(max_gain_db, -20 log10(peak)) / 20))
+//   derivator                         (dataset.py:24-29,244-245: lfilter([.5, -.5], [1], x) per row, float64, zero state)
+// Second launch of rh_feed_batch_post_i16_f32: feed_pitch_kernel<true> left the float64 rows and one peak per row; here a
+// workgroup takes kPostTile samples of one row, thread 0 reduces the n_channels peaks of the row's item in channel order and
+// forms the gain in float64, and every thread applies gain and difference and rounds ONCE to float32 (what the reference's
+// last astype does to its float64 rows).  x[n - 1] is read from the workspace, so neither the chunk seam of the first kernel
+// nor a tile seam of this one is special; only n = 0 is (zero initial state).  Scalar float stores: `out` may be 4-byte aligned.
+constexpr int kPostTile = 2048;
+
+__global__ __launch_bounds__(256) void feed_post_kernel(const double* __restrict__ ws, const double* __restrict__ peaks,
+                                                        const rh_feed_pitch_row* __restrict__ rows, int n_signal, int tiles,
+                                                        int n_channels, int normalize, double max_gain_db, int derivative,
+                                                        float* __restrict__ out) {
+    __shared__ double gain_s;
+    const int r = blockIdx.x / tiles;
+    const int t0 = (blockIdx.x % tiles) * kPostTile;
+    const int len = min(kPostTile, n_signal - t0);
+    const long base = (long)r * n_signal;
+    if (rows[r].mute) {                         // RandomMute runs behind both steps: the finished item times 0
+        for (int i = threadIdx.x; i < len; i += 256) out[base + t0 + i] = 0.f;
+        return;
+    }
+    if (threadIdx.x == 0) {
+        double gain = 1.0;
+        if (normalize) {
+            const int item = r / n_channels;
+            double peak = 0.0;
+            for (int c = 0; c < n_channels; ++c) peak = fmax(peak, peaks[item * n_channels + c]);
+            if (peak != 0.0) gain = pow(10.0, fmin(max_gain_db, -(20.0 * log10(peak))) / 20.0);
+        }
+        gain_s = gain;
+    }
+    __syncthreads();
+    const double gain = gain_s;
+    for (int i = threadIdx.x; i < len; i += 256) {
+        const int n = t0 + i;
+        double y = ws[base + n] * gain;
+        if (derivative) {
+            const double prev = n > 0 ? ws[base + n - 1] * gain : 0.0;
+            y = 0.5 * y - 0.5 * prev;
+        }
+        out[base + n] = (float)y;
+    }
+}
+
+// the checks of the pitched entry points on the host copy of the row table
+int feed_check_rows(const char* what, int64_t pcm_samples, const rh_feed_pitch_row* rows, const double* taps, int32_t n_taps,
+                    int32_t n_rows, int32_t n_signal) {
+    for (int r = 0; r < n_rows; ++r) {
+        const rh_feed_pitch_row& w = rows[r];
+        RH_REQUIRE(w.up >= 1 && w.down >= 1 && w.up <= kMaxFactor && w.down <= kMaxFactor, RH_ERR_INVALID,
+                   "%s: row %d: ratio %d/%d outside 1..%d", what, r, w.up, w.down, kMaxFactor);
+        RH_REQUIRE(w.length >= 1 && w.base >= 0 && w.base <= pcm_samples - w.length, RH_ERR_INVALID,
+                   "%s: row %d: item outside the PCM buffer", what, r);
+        const int g = feed_gcd(w.up, w.down);
+        const int up = w.up / g, down = w.down / g;
+        const int64_t n_out = ((int64_t)w.length * up + down - 1) / down;
+        RH_REQUIRE(w.in_point >= 0 && w.in_point <= n_out - n_signal, RH_ERR_INVALID,
+                   "%s: row %d: window [%lld, %lld) outside the %lld resampled samples", what, r, (long long)w.in_point,
+                   (long long)w.in_point + n_signal, (long long)n_out);
+        if (up != down && !w.mute) {
+            const int H = 10 * std::max(up, down);
+            RH_REQUIRE(taps && w.tap_offset >= 0 && w.tap_offset <= n_taps - (2 * H + 1), RH_ERR_INVALID,
+                       "%s: row %d: %d taps at offset %d outside the table of %d", what, r, 2 * H + 1, w.tap_offset, n_taps);
+            RH_REQUIRE(up * feed_tap_stride(up, H) <= kTapSlots, RH_ERR_INVALID, "%s: row %d: taps exceed the LDS table", what, r);
+        }
+    }
+    return RH_OK;
 }
 
 }  // namespace
@@ -168,26 +266,45 @@ extern "C" int rh_feed_batch_pitch_i16_f32(const int16_t* pcm, int64_t pcm_sampl
                "feed_batch_pitch: bad sizes");
     if (n_rows == 0) return RH_OK;
     RH_REQUIRE(pcm && rows && rows_dev && noise && out, RH_ERR_INVALID, "feed_batch_pitch: null pointer");
-    for (int r = 0; r < n_rows; ++r) {
-        const rh_feed_pitch_row& w = rows[r];
-        RH_REQUIRE(w.up >= 1 && w.down >= 1 && w.up <= kMaxFactor && w.down <= kMaxFactor, RH_ERR_INVALID,
-                   "feed_batch_pitch: row %d: ratio %d/%d outside 1..%d", r, w.up, w.down, kMaxFactor);
-        RH_REQUIRE(w.length >= 1 && w.base >= 0 && w.base <= pcm_samples - w.length, RH_ERR_INVALID,
-                   "feed_batch_pitch: row %d: item outside the PCM buffer", r);
-        const int g = feed_gcd(w.up, w.down);
-        const int up = w.up / g, down = w.down / g;
-        const int64_t n_out = ((int64_t)w.length * up + down - 1) / down;
-        RH_REQUIRE(w.in_point >= 0 && w.in_point <= n_out - n_signal, RH_ERR_INVALID,
-                   "feed_batch_pitch: row %d: window [%lld, %lld) outside the %lld resampled samples", r, (long long)w.in_point,
-                   (long long)w.in_point + n_signal, (long long)n_out);
-        if (up != down && !w.mute) {
-            const int H = 10 * std::max(up, down);
-            RH_REQUIRE(taps && w.tap_offset >= 0 && w.tap_offset <= n_taps - (2 * H + 1), RH_ERR_INVALID,
-                       "feed_batch_pitch: row %d: %d taps at offset %d outside the table of %d", r, 2 * H + 1, w.tap_offset, n_taps);
-            RH_REQUIRE(up * feed_tap_stride(up, H) <= kTapSlots, RH_ERR_INVALID, "feed_batch_pitch: row %d: taps exceed the LDS table", r);
-        }
-    }
-    hipLaunchKernelGGL(feed_pitch_kernel, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, pcm, rows_dev, taps, noise, n_signal,
-                       1.0 / (double)(1ll << bit_depth), out);
+    if (const int rc = feed_check_rows("feed_batch_pitch", pcm_samples, rows, taps, n_taps, n_rows, n_signal)) return rc;
+    hipLaunchKernelGGL(feed_pitch_kernel<false>, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, pcm, rows_dev, taps, noise,
+                       n_signal, 1.0 / (double)(1ll << bit_depth), out, (double*)nullptr, (double*)nullptr);
     return rh_check_launch("feed_batch_pitch");
+}
+
+extern "C" int64_t rh_feed_post_workspace_bytes(int32_t n_rows, int32_t n_signal) {
+    if (n_rows < 0 || n_signal <= 0) return -1;
+    return ((int64_t)n_rows * n_signal + n_rows) * (int64_t)sizeof(double);      // the float64 rows, then one peak per row
+}
+
+extern "C" int rh_feed_batch_post_i16_f32(const int16_t* pcm, int64_t pcm_samples, const rh_feed_pitch_row* rows,
+                                          const rh_feed_pitch_row* rows_dev, const double* taps, int32_t n_taps,
+                                          const float* noise, int32_t n_rows, int32_t n_signal, int32_t bit_depth,
+                                          int32_t n_channels, int32_t normalize, double max_gain_db, int32_t derivative,
+                                          void* workspace, int64_t workspace_bytes, float* out, rh_stream_t stream) {
+    RH_REQUIRE(n_rows >= 0 && n_signal > 0 && bit_depth > 0 && bit_depth < 32 && pcm_samples >= 0 && n_taps >= 0, RH_ERR_INVALID,
+               "feed_batch_post: bad sizes");
+    RH_REQUIRE(n_channels >= 1 && n_rows % n_channels == 0, RH_ERR_INVALID,
+               "feed_batch_post: %d rows are not whole items of %d channels", n_rows, n_channels);
+    RH_REQUIRE(std::isfinite(max_gain_db), RH_ERR_INVALID, "feed_batch_post: max_gain_db is not finite");
+    if (!normalize && !derivative)              // nothing behind Dequantize: the pitched feed itself, no workspace needed
+        return rh_feed_batch_pitch_i16_f32(pcm, pcm_samples, rows, rows_dev, taps, n_taps, noise, n_rows, n_signal, bit_depth, out,
+                                           stream);
+    if (n_rows == 0) return RH_OK;
+    RH_REQUIRE(pcm && rows && rows_dev && noise && out, RH_ERR_INVALID, "feed_batch_post: null pointer");
+    const int64_t need = rh_feed_post_workspace_bytes(n_rows, n_signal);
+    RH_REQUIRE(workspace && workspace_bytes >= need, RH_ERR_INVALID, "feed_batch_post: workspace of %lld bytes, %lld needed",
+               (long long)workspace_bytes, (long long)need);
+    RH_REQUIRE((uintptr_t)workspace % 8 == 0, RH_ERR_INVALID, "feed_batch_post: workspace is not 8-byte aligned");
+    const int tiles = (n_signal + kPostTile - 1) / kPostTile;
+    RH_REQUIRE((int64_t)n_rows * tiles <= 0x7fffffffll, RH_ERR_INVALID, "feed_batch_post: too many tiles for one launch");
+    if (const int rc = feed_check_rows("feed_batch_post", pcm_samples, rows, taps, n_taps, n_rows, n_signal)) return rc;
+    double* ws = (double*)workspace;
+    double* peaks = ws + (int64_t)n_rows * n_signal;
+    hipLaunchKernelGGL(feed_pitch_kernel<true>, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, pcm, rows_dev, taps, noise,
+                       n_signal, 1.0 / (double)(1ll << bit_depth), out, ws, peaks);
+    if (const int rc = rh_check_launch("feed_batch_post")) return rc;
+    hipLaunchKernelGGL(feed_post_kernel, dim3(n_rows * tiles), dim3(256), 0, (hipStream_t)stream, (const double*)ws,
+                       (const double*)peaks, rows_dev, n_signal, tiles, n_channels, normalize, max_gain_db, derivative, out);
+    return rh_check_launch("feed_batch_post: normalize / derivative");
 }

@@ -14,6 +14,17 @@ a random ratio up / down, padtype='mean') and ``p_mute`` the ``RandomMute`` of r
 (rave/transforms.py:168-177), both in the same launch (rh_feed_batch_pitch_i16_f32): the polyphase filter is evaluated only
 for the samples inside the crop window.  ``RandomGain`` (gain.gin) needs nothing: it returns its input unchanged
 (rave/transforms.py:163).  The draws are host logic (``pitch_factors``, ``PitchTable``, ``draw_batch``) and need no GPU.
+
+``normalize=True`` and ``derivative=True`` are the two steps ``rave train --normalize`` / ``--derivative`` put between
+Dequantize and the augmentations (scripts/train.py:61-63,160-167): ``normalize_signal`` (rave/dataset.py:196-204,241-242: one
+gain per item from the peak over all its channels, capped at ``max_gain_db`` = 30 dB) and the derivator (rave/dataset.py:24-29,
+244-245: ``lfilter([.5, -.5], [1], x)``).  They run in a launch pair (rh_feed_batch_post_i16_f32): the chain kernel keeps its
+float64 rows and one peak per row in a workspace cached on the feed, a second kernel applies gain and difference in float64 and
+rounds once to float32.
+
+Not built: ``Resample`` (a dataset stored at another rate than ``sr``: torchaudio.functional.resample, rave/dataset.py:238-239),
+``Compress`` / ``RandomCompress`` (sox ``compand`` through torchaudio, rave/transforms.py:114-145) and ``FrequencyMasking``
+(commented out in the only config that names it).
 """
 from __future__ import annotations
 
@@ -126,6 +137,14 @@ def draw_batch(rng: np.random.Generator, n_items: int, length: int, batch: int, 
     return items, in_points, angles, ratios
 
 
+def check_max_gain_db(max_gain_db) -> float:
+    """The gain cap of normalize_signal (rave/dataset.py:196) as a finite float; anything else is an error."""
+    if isinstance(max_gain_db, bool) or not isinstance(max_gain_db, (int, float, np.integer, np.floating)) \
+            or not math.isfinite(max_gain_db):
+        raise RuntimeError(f"GpuBatchFeed: max_gain_db must be a finite number of dB, not {max_gain_db!r}")
+    return float(max_gain_db)
+
+
 # mirror of ``rh_feed_pitch_row`` (include/rave_hip.h)
 ROW_DTYPE = np.dtype([("base", np.int64), ("in_point", np.int64), ("mean", np.float64), ("coef", np.float64, 5),
                       ("length", np.int32), ("up", np.int32), ("down", np.int32), ("tap_offset", np.int32),
@@ -135,10 +154,14 @@ ROW_DTYPE = np.dtype([("base", np.int64), ("in_point", np.int64), ("mean", np.fl
 class GpuBatchFeed:
     """``pcm``: int16 tensor (n_items, n_channels, length) on the GPU.  ``sample`` returns a (B, n_channels, n_signal)
     float32 minibatch ready for ``RAVE.training_step``.  ``rand_pitch=(lo, hi)``: RandomPitch(n_signal, [lo, hi], max_factor,
-    prob=p_pitch) in front of the crop; ``p_mute``: RandomMute(p_mute) at the end of the chain (module docstring)."""
+    prob=p_pitch) in front of the crop; ``p_mute``: RandomMute(p_mute) at the end of the chain; ``normalize`` / ``derivative``:
+    normalize_signal(x, max_gain_db) and the derivator between Dequantize and RandomMute (module docstring)."""
 
     def __init__(self, pcm: torch.Tensor, sr: int = 44100, seed: int = 0, p_mangle: float = .8, bit_depth: int = 16,
-                 rand_pitch: Optional[Sequence[float]] = None, p_pitch: float = .5, max_factor: int = 20, p_mute: float = 0.):
+                 rand_pitch: Optional[Sequence[float]] = None, p_pitch: float = .5, max_factor: int = 20, p_mute: float = 0.,
+                 normalize: bool = False, derivative: bool = False, max_gain_db: float = 30.):
+        self.normalize, self.derivative, self.max_gain_db = bool(normalize), bool(derivative), check_max_gain_db(max_gain_db)
+        self.workspace = None
         if pcm.dtype != torch.int16 or pcm.dim() != 3 or not pcm.is_cuda:
             raise RuntimeError("GpuBatchFeed: pcm must be an int16 (items, channels, length) tensor on the GPU")
         if not 0. <= p_mute <= 1.:
@@ -193,7 +216,8 @@ class GpuBatchFeed:
         out = torch.empty(batch, n_ch, n_signal, device=dev, dtype=torch.float32)
         pitched = ratios is not None and any(r is not None for r in ratios)
         muted = mute is not None and any(mute)
-        if not (pitched or muted):
+        post = self.normalize or self.derivative
+        if not (pitched or muted or post):
             off = np.empty(rows, dtype=np.int64)
             coef = np.full((rows, 5), np.nan, dtype=np.float64)
             for b in range(batch):
@@ -229,6 +253,16 @@ class GpuBatchFeed:
                     row["tap_offset"] = self._tap_offset(ratio)
         table_d = torch.from_numpy(table.view(np.uint8)).to(dev)
         n_taps = 0 if self.taps is None else self.taps.numel()
+        if post:
+            need = L.lib.rh_feed_post_workspace_bytes(rows, n_signal)
+            if self.workspace is None or self.workspace.numel() * 8 < need:            # regrown only when rows x n_signal grows
+                self.workspace = torch.empty(need // 8, device=dev, dtype=torch.float64)
+            L.check(L.lib.rh_feed_batch_post_i16_f32(L.ptr(self.pcm), self.pcm.numel(), table.ctypes.data, L.ptr(table_d),
+                                                     L.ptr(self.taps), n_taps, L.ptr(noise), rows, n_signal, self.bit_depth,
+                                                     n_ch, int(self.normalize), self.max_gain_db, int(self.derivative),
+                                                     L.ptr(self.workspace), self.workspace.numel() * 8, L.ptr(out), L.stream()),
+                    "feed_batch_post")
+            return out
         L.check(L.lib.rh_feed_batch_pitch_i16_f32(L.ptr(self.pcm), self.pcm.numel(), table.ctypes.data, L.ptr(table_d),
                                                   L.ptr(self.taps), n_taps, L.ptr(noise), rows, n_signal, self.bit_depth,
                                                   L.ptr(out), L.stream()), "feed_batch_pitch")
