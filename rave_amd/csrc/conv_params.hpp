@@ -156,6 +156,24 @@ struct RhWgradArmed {
 RhWgradArmed rh_wgrad_take_armed(bool may_defer);
 int rh_wgrad_run(const rh_conv1d_desc* d, const float* dy, const float* x, const float* alpha, float* dw, float* dbias, void* ws,
                  int64_t ws_bytes, hipStream_t stream, const RhWgradArmed& armed, const RhWnTail* tail = nullptr);
+int64_t rh_wgrad_workspace(const rh_conv1d_desc* d);
+int rh_reduce_wn_bwd_launch(const float* part, int Z, long M, long N, const float* v, const float* g, const float* norms,
+                            float* dv, float* dg, hipStream_t stream, bool* used);
+// The weight gradient on the 16-bit matrix cores (conv_wgrad_x6.hip) as the route of conv_wgrad.hip holds it: planned ONCE per
+// call by rh_wgrad_x6_plan (false = the call does not take this path; ranges: the slots of R and S, null = not armed), then
+// launched, or described by the two formatters, from that plan.  The kernels' parameter block and the tile plan stay private
+// to conv_wgrad_x6.hip (the block's type is part of the kernels' names); `state` carries them.
+struct RhWx6Planned {
+    int Z;                      // K slices; > 1: the launch leaves the partials [Z][M][C*T] at the head of the scratch
+    int64_t ws_bytes;           // scratch the launch needs: those partials + the row-sum partials [Z][M] (always reserved)
+    alignas(16) unsigned char state[640];
+};
+bool rh_wgrad_x6_plan(const WgradP& w, const unsigned* r_range, const unsigned* s_range, RhWx6Planned* out);
+// rsum_out != null: also the row sums of R over (batch, position) -- the bias gradient when R = dy -- from the same pass, reduced
+// here.  The weight partials of a split K range (Z > 1) are left to the caller; Z == 1 writes dw itself.
+int rh_wgrad_x6_launch(const RhWx6Planned& planned, float* dw, float* rsum_out, void* ws, hipStream_t stream);
+void rh_wgrad_x6_plan_info(const RhWx6Planned& planned, int32_t* out4);          // rh_conv1d_bwd_weight_plan_info's numbers
+void rh_wgrad_x6_instance_info(const RhWx6Planned& planned, int32_t* out16);     // rh_conv1d_bwd_weight_instance_info's, family 1
 
 int rh_conv_fill_fwd(const rh_conv1d_desc* d, ConvP* p);
 int rh_conv_fill_dgrad(const rh_conv1d_desc* d, ConvP* p);

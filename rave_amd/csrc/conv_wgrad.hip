@@ -647,7 +647,7 @@ WPlan plan(const WgradP& p) {
     return w;
 }
 
-// The five tile shapes <TM, TN, WM, WN> of the two kernels, by the plan's workgroup tile (rh_wgrad_run instantiates exactly these).
+// The five tile shapes <TM, TN, WM, WN> of the two kernels, by the plan's workgroup tile (route_wgrad1 instantiates exactly these).
 struct WShape { int tm, tn, wm, wn; };
 WShape w_shape(const WPlan& w) {
     if (w.bm == 32) return WShape{1, 2, 1, 4};
@@ -659,7 +659,7 @@ WShape w_shape(const WPlan& w) {
 
 // The instance of a plan and a tile shape: which kernel, and for wgrad_dma_kernel the staging (vec) and which operand carries
 // LeakyReLU (0 none, 1 R, 2 S).  w_configure fills the launch fields of p for it; launch_w launches what it says, and
-// rh_conv1d_bwd_weight_instance_info reports it.
+// route_wgrad1 reports it.
 struct WInst { int dma, vec, leaky; size_t lds; };
 
 WInst w_configure(WgradP& p, const WPlan& w, const WShape& sh) {
@@ -735,80 +735,6 @@ int launch_w(WgradP& p, const WPlan& w, hipStream_t stream) {
 
 }  // namespace
 
-int64_t rh_wgrad_x6_workspace(const WgradP& w);
-int rh_wgrad_x6_launch(const WgradP& w, float* dw, float* rsum_out, void* ws, hipStream_t stream, bool* used, int* left_z,
-                       const unsigned* r_range, const unsigned* s_range);
-int rh_reduce_wn_bwd_launch(const float* part, int Z, long M, long N, const float* v, const float* g, const float* norms,
-                            float* dv, float* dg, hipStream_t stream, bool* used);
-
-extern "C" int rh_conv1d_bwd_weight_kernel_family(const rh_conv1d_desc* d) {
-    if (!d || d->batch <= 0) return 0;
-    WgradP p{};
-    fill(d, &p);
-    if (rh_smallc_wgrad_eligible(d)) return 2;
-    alignas(16) static const float dummy[4] = {0.f, 0.f, 0.f, 0.f};
-    p.R = dummy; p.S = dummy;
-    return d->act != RH_ACT_SNAKE && rh_wgrad_x6_workspace(p) >= 0 ? 1 : 0;
-}
-
-bool rh_wgrad_x6_plan_info(const WgradP& w, int32_t* out4);
-
-extern "C" int rh_conv1d_bwd_weight_plan_info(const rh_conv1d_desc* d, int32_t* out4) {
-    if (!d || !out4) return RH_ERR_INVALID;
-    for (int i = 0; i < 4; ++i) out4[i] = 0;
-    if (d->batch <= 0 || rh_conv1d_bwd_weight_kernel_family(d) != 1) return RH_OK;
-    WgradP p{};
-    fill(d, &p);
-    alignas(16) static const float dummy[4] = {0.f, 0.f, 0.f, 0.f};
-    p.R = dummy; p.S = dummy;
-    (void)rh_wgrad_x6_plan_info(p, out4);
-    return RH_OK;
-}
-
-bool rh_wgrad_x6_instance_info(const WgradP& w, bool armed, int32_t* out16);
-
-// Which kernel instance rh_wgrad_run would launch: the same three questions in the same order, answered by the code the launch
-// runs (rh_smallc_wgrad_eligible; plan_wx6 + wx6_inst_of; plan + w_shape + w_configure).
-extern "C" int rh_conv1d_bwd_weight_instance_info(const rh_conv1d_desc* d, int dy_aligned16, int x_aligned16, int ranges_armed,
-                                                  int32_t* out16) {
-    if (!d || !out16) return RH_ERR_INVALID;
-    for (int i = 0; i < 16; ++i) out16[i] = 0;
-    out16[0] = -1;
-    if (d->batch <= 0 || d->l_in <= 0 || d->l_out <= 0 || d->inner <= 0 || d->kernel <= 0 || d->kernel > kMaxTaps) return RH_OK;
-    WgradP p{};
-    fill(d, &p);
-    if (rh_smallc_wgrad_eligible(d)) { out16[0] = 2; return RH_OK; }
-    alignas(16) static const float dummy[8] = {};
-    const float* const dy = dummy + (dy_aligned16 ? 0 : 1);
-    const float* const x = dummy + (x_aligned16 ? 0 : 1);
-    if (!d->transposed) { p.R = dy; p.S = x; }
-    else                { p.R = x; p.S = dy; }
-    if (d->act != RH_ACT_SNAKE && rh_wgrad_x6_instance_info(p, !RH_X6_F16 || ranges_armed != 0, out16)) return RH_OK;
-    const WPlan w = plan(p);
-    const WShape sh = w_shape(w);
-    const WInst in = w_configure(p, w, sh);
-    const int32_t v[16] = {0, w.bm, w.bn, in.dma, in.vec, in.leaky, w.rk, w.Z, w.chunks_per_z, w.total_chunks, w.chunks_per_b,
-                           p.nc_max, p.r_act, p.s_act, sh.wm * sh.wn, w.mt * w.ct};
-    for (int i = 0; i < 16; ++i) out16[i] = v[i];
-    return RH_OK;
-}
-
-int64_t rh_wgrad_workspace(const rh_conv1d_desc* d) {
-    WgradP p{};
-    fill(d, &p);
-    const int64_t bias = rh_bias_grad_workspace(d->c_out);
-    if (rh_smallc_wgrad_eligible(d)) return bias + rh_smallc_wgrad_workspace(d);
-    int64_t x6 = -1;
-    if (d->act != RH_ACT_SNAKE) {      // exact f32 on the 16-bit matrix cores (conv_wgrad_x6.hip) when the geometry fits
-        x6 = rh_wgrad_x6_workspace(p);
-        if (x6 >= 0 && !RH_X6_F16) return bias + x6;
-    }
-    // (f16 build: a call without range slots falls back to the f32-input kernels -- the scratch covers both plans)
-    const WPlan w = plan(p);
-    const int64_t f32 = w.Z <= 1 ? 0 : (int64_t)w.Z * p.M * p.C * p.T * (int64_t)sizeof(float);
-    return bias + (x6 > f32 ? x6 : f32);
-}
-
 extern "C" int rh_weight_norm_bwd_f32(const float* dw, const float* v, const float* g, const float* norms, int64_t rows,
                                       int64_t cols, float* dv, float* dg, rh_stream_t stream);
 
@@ -856,80 +782,116 @@ RhWgradArmed rh_wgrad_take_armed(bool may_defer) {
     return a;
 }
 
-int rh_wgrad_run(const rh_conv1d_desc* d, const float* dy, const float* x, const float* alpha,
-                 float* dw, float* dbias, void* ws, int64_t ws_bytes, hipStream_t stream, const RhWgradArmed& armed,
-                 const RhWnTail* tail) {
+namespace {
+
+// What route_wgrad1 reports instead of launching (include/rave_hip.h documents the numbers; inst[0] is the family).
+struct WRoute {
+    int32_t inst[16], plan[4];
+    int64_t scratch[3];      // by family: bytes its plan wants behind the bias scratch (family 0 is sized beside family 1: the
+                             // same call falls back to it without range slots); family 2: in all, its bias gradient included
+};
+
+// The one tail: Z K-slice partials of M x N floats lie in part (Z <= 1: dw is complete).  Fused weight-norm reduction, or deferred
+// item, or the plain reduction into dw and, with a tail, on through dw.  (defer is null whenever tail is set, so the order of the
+// first two decides nothing.)
+int finish_dw(const float* part, int Z, long M, long N, float* dw, const RhWnTail* tail, rh_reduce_item* defer, hipStream_t stream) {
+    if (Z > 1) {
+        if (tail) {
+            bool fused = false;
+            if (int e = rh_reduce_wn_bwd_launch(part, Z, M, N, tail->v, tail->g, tail->norms, tail->dv, tail->dg, stream, &fused)) return e;
+            if (fused) return RH_OK;
+        }
+        if (defer) {        // the caller batches this layer's reduction with its neighbours'
+            defer->part = part; defer->out = dw; defer->n = M * N; defer->Z = Z;
+            return RH_OK;
+        }
+        if (int e = rh_reduce_partials_launch(part, dw, M * N, Z, stream, "conv1d_bwd_weight_reduce")) return e;
+    }
+    if (!tail) return RH_OK;
+    return rh_weight_norm_bwd_f32(dw, tail->v, tail->g, tail->norms, M, N, tail->dv, tail->dg, (rh_stream_t)stream);
+}
+
+// The one place that decides which kernel a 1-D weight-gradient call runs, in the order it tries them: the vector-ALU first-layer
+// kernel (family 2), the 16-bit-matrix-core kernels where the call is armed and plan_wx6 accepts (family 1, planned once), else the
+// f32-input MFMA kernels (family 0).  info == null: launch it, bias gradient and tail included; else fill *info (zeroed by the
+// caller) and launch nothing -- dy / x then only carry their alignment, the ranges only whether they are armed.
+int route_wgrad1(const rh_conv1d_desc* d, const float* dy, const float* x, const float* alpha, float* dw, float* dbias, void* ws,
+                 int64_t ws_bytes, const RhWgradArmed& armed, const RhWnTail* tail, hipStream_t stream, WRoute* info) {
     rh_reduce_item* const defer = tail ? nullptr : armed.defer;
     WgradP p{};
     fill(d, &p);
-    const unsigned* const dy_range = armed.dy_range;
-    const unsigned* const x_range = armed.x_range;
-    const bool have_ranges = !RH_X6_F16 || (dy_range && x_range);
-    auto through_dw = [&](int e) {
-        if (e || !tail) return e;
-        return rh_weight_norm_bwd_f32(dw, tail->v, tail->g, tail->norms, p.M, (int64_t)p.C * p.T, tail->dv, tail->dg, (rh_stream_t)stream);
-    };
     if (!d->transposed) { p.R = dy; p.S = x; p.r_alpha = nullptr; p.s_alpha = alpha; }
     else                { p.R = x; p.S = dy; p.r_alpha = alpha; p.s_alpha = nullptr; }
-    const long nw = (long)p.M * p.C * p.T;
+    const long N = (long)p.C * p.T;
     const int64_t bias_ws = rh_bias_grad_workspace(d->c_out);
     if (rh_smallc_wgrad_eligible(d)) {       // 1- / 2-channel first layers: vector-ALU kernel, bias gradient included
         const int64_t need = rh_smallc_wgrad_workspace(d);
+        if (info) {
+            info->inst[0] = 2;
+            info->scratch[2] = need;
+            return RH_OK;
+        }
         RH_REQUIRE(ws && ws_bytes >= need, RH_ERR_WORKSPACE, "conv1d_bwd_weight: workspace %lld B < %lld B",
                    (long long)ws_bytes, (long long)need);
-        return through_dw(rh_smallc_wgrad(d, dy, x, dw, dbias, ws, stream));
+        if (int e = rh_smallc_wgrad(d, dy, x, dw, dbias, ws, stream)) return e;
+        return finish_dw(nullptr, 1, p.M, N, dw, tail, nullptr, stream);
     }
-    // Conv1d on the bf16x6 weight-gradient kernel: the bias gradient (row sums of dy) comes out of the same pass
-    const bool x6_path = have_ranges && d->act != RH_ACT_SNAKE && p.B > 0 && p.r_row > 0 && rh_wgrad_x6_workspace(p) >= 0;
-    const bool fuse_bias = x6_path && !d->transposed && dbias != nullptr;
-    if (dbias && d->batch > 0 && !fuse_bias) {
-        RH_REQUIRE(ws && ws_bytes >= bias_ws, RH_ERR_WORKSPACE, "conv1d_bwd_weight: workspace %lld B < %lld B",
-                   (long long)ws_bytes, (long long)bias_ws);
-        // the first c_out*64 floats of the workspace; the split-K partials follow
-        if (int e = rh_bias_grad_launch(dy, nullptr, (float*)ws, dbias, d->batch, d->c_out,
-                                        (long)d->l_out * d->inner, RH_ACT_NONE, 0.f, stream))
-            return e;
-    }
-    ws = ws ? (void*)((char*)ws + bias_ws) : nullptr;
-    ws_bytes = ws_bytes > bias_ws ? ws_bytes - bias_ws : 0;
-    if (p.B <= 0 || p.r_row <= 0) {
-        (void)hipMemsetAsync(dw, 0, nw * sizeof(float), stream);
-        if (dbias) (void)hipMemsetAsync(dbias, 0, d->c_out * sizeof(float), stream);
-        return through_dw(RH_OK);
-    }
-    if (d->act != RH_ACT_SNAKE && have_ranges) {
-        const int64_t x6 = rh_wgrad_x6_workspace(p);
-        if (x6 >= 0) {
-            RH_REQUIRE(x6 == 0 || (ws && ws_bytes >= x6), RH_ERR_WORKSPACE,
-                       "conv1d_bwd_weight: workspace %lld B < %lld B", (long long)ws_bytes, (long long)x6);
-            bool used = false;
-            int left_z = 0;      // > 0: the partials were left unreduced in ws for the fused tail
-            if (int e = rh_wgrad_x6_launch(p, dw, fuse_bias ? dbias : nullptr, ws, stream, &used, (tail || defer) ? &left_z : nullptr,
-                                           d->transposed ? x_range : dy_range, d->transposed ? dy_range : x_range))
+    // exact f32 on the 16-bit matrix cores (conv_wgrad_x6.hip) when the geometry fits and, in the f16 build, both range slots are
+    // armed; for Conv1d the bias gradient (row sums of dy) comes out of the same pass
+    const bool empty = p.B <= 0 || p.r_row <= 0;
+    const bool have_ranges = !RH_X6_F16 || (armed.dy_range && armed.x_range);
+    RhWx6Planned x6;
+    const bool take_x6 = have_ranges && d->act != RH_ACT_SNAKE && !empty &&
+                         rh_wgrad_x6_plan(p, d->transposed ? armed.x_range : armed.dy_range, d->transposed ? armed.dy_range : armed.x_range, &x6);
+    if (info) {
+        if (take_x6) {
+            info->scratch[1] = x6.ws_bytes;
+            rh_wgrad_x6_plan_info(x6, info->plan);
+            rh_wgrad_x6_instance_info(x6, info->inst);
+        }
+        if (empty || p.inner <= 0) return RH_OK;      // (nothing to plan: the launch only clears dw)
+    } else {
+        const bool fuse_bias = take_x6 && !d->transposed && dbias != nullptr;
+        if (dbias && d->batch > 0 && !fuse_bias) {
+            RH_REQUIRE(ws && ws_bytes >= bias_ws, RH_ERR_WORKSPACE, "conv1d_bwd_weight: workspace %lld B < %lld B",
+                       (long long)ws_bytes, (long long)bias_ws);
+            // the first c_out*64 floats of the workspace; the split-K partials follow
+            if (int e = rh_bias_grad_launch(dy, nullptr, (float*)ws, dbias, d->batch, d->c_out,
+                                            (long)d->l_out * d->inner, RH_ACT_NONE, 0.f, stream))
                 return e;
-            if (used && left_z > 1 && defer) {        // the caller batches this layer's reduction with its neighbours'
-                defer->part = (const float*)ws; defer->out = dw; defer->n = nw; defer->Z = left_z;
-                return RH_OK;
-            }
-            if (used && left_z > 1) {
-                bool fused = false;
-                if (int e = rh_reduce_wn_bwd_launch((const float*)ws, left_z, p.M, (long)p.C * p.T, tail->v, tail->g, tail->norms,
-                                                    tail->dv, tail->dg, stream, &fused))
-                    return e;
-                if (fused) return RH_OK;
-                return through_dw(rh_reduce_partials_launch((const float*)ws, dw, nw, left_z, stream, "conv1d_bwd_weight_reduce"));
-            }
-            if (used) return through_dw(RH_OK);
+        }
+        ws = ws ? (void*)((char*)ws + bias_ws) : nullptr;
+        ws_bytes = ws_bytes > bias_ws ? ws_bytes - bias_ws : 0;
+        if (empty) {
+            (void)hipMemsetAsync(dw, 0, p.M * N * sizeof(float), stream);
+            if (dbias) (void)hipMemsetAsync(dbias, 0, d->c_out * sizeof(float), stream);
+            return finish_dw(nullptr, 1, p.M, N, dw, tail, nullptr, stream);
+        }
+        if (take_x6) {
+            RH_REQUIRE(x6.ws_bytes == 0 || (ws && ws_bytes >= x6.ws_bytes), RH_ERR_WORKSPACE,
+                       "conv1d_bwd_weight: workspace %lld B < %lld B", (long long)ws_bytes, (long long)x6.ws_bytes);
+            if (int e = rh_wgrad_x6_launch(x6, dw, fuse_bias ? dbias : nullptr, ws, stream)) return e;
+            return finish_dw((const float*)ws, x6.Z, p.M, N, dw, tail, defer, stream);
         }
     }
     const WPlan w = plan(p);
-    const int64_t need = w.Z > 1 ? (int64_t)w.Z * nw * (int64_t)sizeof(float) : 0;
+    const WShape sh = w_shape(w);
+    const int64_t need = w.Z > 1 ? (int64_t)w.Z * p.M * N * (int64_t)sizeof(float) : 0;
+    if (info) {
+        info->scratch[0] = need;
+        if (take_x6) return RH_OK;      // (only sized)
+        const WInst in = w_configure(p, w, sh);
+        const int32_t v[16] = {0, w.bm, w.bn, in.dma, in.vec, in.leaky, w.rk, w.Z, w.chunks_per_z, w.total_chunks, w.chunks_per_b,
+                               p.nc_max, p.r_act, p.s_act, sh.wm * sh.wn, w.mt * w.ct};
+        for (int i = 0; i < 16; ++i) info->inst[i] = v[i];
+        return RH_OK;
+    }
     RH_REQUIRE(need == 0 || (ws && ws_bytes >= need), RH_ERR_WORKSPACE,
                "conv1d_bwd_weight: workspace %lld B < %lld B", (long long)ws_bytes, (long long)need);
     p.out = w.Z > 1 ? (float*)ws : dw;
     int e;
-    const WShape sh = w_shape(w);
     const auto is = [&](int tm, int tn, int wm, int wn) { return sh.tm == tm && sh.tn == tn && sh.wm == wm && sh.wn == wn; };
+    // (the five shapes of w_shape; F0_SHAPES in tests/wgrad_matrix.py lists their tiles and must follow)
     if (is(1, 2, 1, 4)) e = launch_w<1, 2, 1, 4>(p, w, stream);
     else if (is(2, 1, 1, 4)) e = launch_w<2, 1, 1, 4>(p, w, stream);
     else if (is(3, 1, 1, 3)) e = launch_w<3, 1, 1, 3>(p, w, stream);
@@ -937,22 +899,57 @@ int rh_wgrad_run(const rh_conv1d_desc* d, const float* dy, const float* x, const
     else if (is(2, 2, 2, 2)) e = launch_w<2, 2, 2, 2>(p, w, stream);
     else RH_REQUIRE(false, RH_ERR_UNSUPPORTED, "conv1d_bwd_weight: no kernel for tile shape %d %d %d %d", sh.tm, sh.tn, sh.wm, sh.wn);
     if (e) return e;
-    if (w.Z > 1) {
-        if (tail) {
-            bool fused = false;
-            if (int e2 = rh_reduce_wn_bwd_launch((const float*)ws, w.Z, p.M, nw / p.M, tail->v, tail->g, tail->norms, tail->dv,
-                                                 tail->dg, stream, &fused))
-                return e2;
-            if (fused) return RH_OK;
-        }
-        if (defer) {
-            defer->part = (const float*)ws; defer->out = dw; defer->n = nw; defer->Z = w.Z;
-            return RH_OK;
-        }
-        reduce_partials_go((const float*)ws, dw, nw, w.Z, stream);
-        return through_dw(rh_check_launch("conv1d_bwd_weight_reduce"));
-    }
-    return through_dw(RH_OK);
+    return finish_dw((const float*)ws, w.Z, p.M, N, dw, tail, defer, stream);
+}
+
+// The route's report on a call with dy / x (not) 16-byte aligned and the range slots (not) armed: stand-ins, nothing is dereferenced
+WRoute report_wgrad1(const rh_conv1d_desc* d, bool dy_aligned16, bool x_aligned16, bool ranges_armed) {
+    alignas(16) static const float dummy[8] = {};
+    static const unsigned slot[kRangeSlotWords] = {};
+    const unsigned* const range = ranges_armed ? slot : nullptr;
+    WRoute r{};
+    (void)route_wgrad1(d, dummy + (dy_aligned16 ? 0 : 1), dummy + (x_aligned16 ? 0 : 1), nullptr, nullptr, nullptr, nullptr, 0,
+                       RhWgradArmed{nullptr, range, range}, nullptr, nullptr, &r);
+    return r;
+}
+
+}  // namespace
+
+// (answers as if the call were armed; an empty batch counts as family 0)
+extern "C" int rh_conv1d_bwd_weight_kernel_family(const rh_conv1d_desc* d) {
+    if (!d || d->batch <= 0) return 0;
+    return report_wgrad1(d, true, true, true).inst[0];
+}
+
+extern "C" int rh_conv1d_bwd_weight_plan_info(const rh_conv1d_desc* d, int32_t* out4) {
+    if (!d || !out4) return RH_ERR_INVALID;
+    const WRoute r = d->batch > 0 ? report_wgrad1(d, true, true, true) : WRoute{};
+    for (int i = 0; i < 4; ++i) out4[i] = r.plan[i];
+    return RH_OK;
+}
+
+extern "C" int rh_conv1d_bwd_weight_instance_info(const rh_conv1d_desc* d, int dy_aligned16, int x_aligned16, int ranges_armed,
+                                                  int32_t* out16) {
+    if (!d || !out16) return RH_ERR_INVALID;
+    for (int i = 0; i < 16; ++i) out16[i] = 0;
+    out16[0] = -1;
+    if (d->batch <= 0 || d->l_in <= 0 || d->l_out <= 0 || d->inner <= 0 || d->kernel <= 0 || d->kernel > kMaxTaps) return RH_OK;
+    const WRoute r = report_wgrad1(d, dy_aligned16 != 0, x_aligned16 != 0, ranges_armed != 0);
+    for (int i = 0; i < 16; ++i) out16[i] = r.inst[i];
+    return RH_OK;
+}
+
+int64_t rh_wgrad_workspace(const rh_conv1d_desc* d) {
+    const WRoute r = report_wgrad1(d, true, true, true);
+    // (f16 build: a call without range slots falls back to the f32-input kernels -- the scratch covers both plans)
+    const int64_t both = r.scratch[1] > r.scratch[0] ? r.scratch[1] : r.scratch[0];
+    return rh_bias_grad_workspace(d->c_out) + (r.inst[0] == 2 || !RH_X6_F16 ? r.scratch[r.inst[0]] : both);
+}
+
+int rh_wgrad_run(const rh_conv1d_desc* d, const float* dy, const float* x, const float* alpha,
+                 float* dw, float* dbias, void* ws, int64_t ws_bytes, hipStream_t stream, const RhWgradArmed& armed,
+                 const RhWnTail* tail) {
+    return route_wgrad1(d, dy, x, alpha, dw, dbias, ws, ws_bytes, armed, tail, stream, nullptr);
 }
 
 int rh_reduce_partials_launch(const float* part, float* out, long n, int Z, hipStream_t stream, const char* what) {

@@ -20,7 +20,7 @@
 // Layout of this file: emit (conversion of 8 samples), the STAGING LAYER (scales, step geometry, R tasks, S tasks, the MFMA k
 // block, the tile store -- each written once), then the kernels, each no more than its LDS layout, its barriers and its main loop
 // over that layer; then the host side: Wx6Env (the switches), plan_wx6 = wx6_eligible -> wx6_choose_tile -> wx6_slice_k,
-// wx6_instance / launch_wx6, and the three entry points.  A further tile shape is a further loop, not a further copy.
+// wx6_instance / launch_wx6, and the entry points: plan once (rh_wgrad_x6_plan), then launch or describe that plan.  A further tile shape is a further loop, not a further copy.
 //
 // Two tile shapes (wx6_choose_tile chooses by the layer):
 //   * wgrad_x6_kernel: four waves, workgroup tile 32 TM WM rows x 64 WN columns, wave tile 32 TM x 64, one LDS stage, two
@@ -41,6 +41,7 @@
 // 90 per pair).  What pays is fewer VALU instructions per sample.
 #include <cstdlib>
 #include <mutex>
+#include <new>
 #include <type_traits>
 #include "conv_params.hpp"
 
@@ -754,73 +755,59 @@ Wx6Launch wx6_instance(const Wx6Inst& in) {
     });
 }
 
+// What rh_wgrad_x6_plan leaves in RhWx6Planned::state.
+struct Wx6Planned {
+    Wx6P p;
+    Wx6Plan pl;
+};
+static_assert(sizeof(Wx6Planned) <= sizeof(RhWx6Planned::state) && alignof(Wx6Planned) <= 16 && std::is_trivially_copyable<Wx6Planned>::value,
+              "RhWx6Planned::state holds a Wx6Planned");
+const Wx6Planned& wx6_planned(const RhWx6Planned& q) { return *reinterpret_cast<const Wx6Planned*>(q.state); }
+
 }  // namespace
 
-// Scratch (bytes) the bf16x6 weight-gradient path wants for its K-slice partials; -1 = geometry not eligible.
-int64_t rh_wgrad_x6_workspace(const WgradP& w) {
-    Wx6P p;
-    Wx6Plan pl{};
-    static const unsigned any_range[kRangeSlotWords] = {};      // planning only: the answer does not depend on the slots
-    if (!plan_wx6(w, &p, &pl, any_range, any_range)) return -1;
+bool rh_wgrad_x6_plan(const WgradP& w, const unsigned* r_range, const unsigned* s_range, RhWx6Planned* out) {
+    Wx6Planned* const q = new (out->state) Wx6Planned{};
+    if (!plan_wx6(w, &q->p, &q->pl, r_range, s_range)) return false;
+    out->Z = q->pl.Z;
     // partial weight tiles (Z > 1) + partial row sums for the fused bias gradient (always reserved)
-    return (pl.Z > 1 ? (int64_t)pl.Z * w.M * w.C * w.T : 0) * (int64_t)sizeof(float) + (int64_t)pl.Z * w.M * (int64_t)sizeof(float);
+    out->ws_bytes = (q->pl.Z > 1 ? (int64_t)q->pl.Z * w.M * w.C * w.T : 0) * (int64_t)sizeof(float) + (int64_t)q->pl.Z * w.M * (int64_t)sizeof(float);
+    return true;
 }
 
-// Diagnostics (rh_conv1d_bwd_weight_plan_info): out4 = {waves per workgroup, workgroups, K slices, plane staging} of the launch
-// rh_wgrad_x6_launch would issue now; false = geometry not eligible.
-bool rh_wgrad_x6_plan_info(const WgradP& w, int32_t* out4) {
-    Wx6P p;
-    Wx6Plan pl{};
-    static const unsigned any_range[kRangeSlotWords] = {};
-    if (!plan_wx6(w, &p, &pl, any_range, any_range)) return false;
+// out4 = {waves per workgroup, workgroups, K slices, plane staging} of the planned launch
+void rh_wgrad_x6_plan_info(const RhWx6Planned& planned, int32_t* out4) {
+    const Wx6Plan& pl = wx6_planned(planned).pl;
     out4[0] = pl.nw > 0 ? pl.nw : 4;
     out4[1] = pl.rt * pl.ct * pl.Z;
     out4[2] = pl.Z;
     out4[3] = pl.planes;
-    return true;
 }
 
-// Diagnostics (rh_conv1d_bwd_weight_instance_info): the instance rh_wgrad_x6_launch would launch for w (w.R carries the
-// alignment of R) -- plan_wx6 + wx6_inst_of, the launch's own code.  armed = the call has its two range slots.  out16 =
+// The instance of the planned launch (the plan's R carries the alignment of R): wx6_inst_of, what the launch itself asks.  out16 =
 // {1, wide, NW or tm, wm, AV, PART, PL, Z, steps_per_z, total_steps, tile rows, tile columns, steps_per_b, p8, chmax, row tiles *
-// column tiles}; false = the call does not take this path.
-bool rh_wgrad_x6_instance_info(const WgradP& w, bool armed, int32_t* out16) {
-    Wx6P p;
-    Wx6Plan pl{};
-    static const unsigned any_range[kRangeSlotWords] = {};
-    const unsigned* const range = armed ? any_range : nullptr;
-    if (!plan_wx6(w, &p, &pl, range, range)) return false;
+// column tiles}
+void rh_wgrad_x6_instance_info(const RhWx6Planned& planned, int32_t* out16) {
+    const Wx6P& p = wx6_planned(planned).p;
+    const Wx6Plan& pl = wx6_planned(planned).pl;
     const Wx6Inst in = wx6_inst_of(p, pl);
     const int32_t v[16] = {1, in.nw > 0, in.nw > 0 ? in.nw : in.tm, in.nw > 0 ? 0 : in.wm, in.av, in.part, in.pl, pl.Z, pl.steps_per_z,
                            p.total_steps, in.nw > 0 ? 96 : 32 * in.tm * in.wm, in.nw > 0 ? 32 * in.nw : 64 * (4 / in.wm), p.steps_per_b,
                            in.pl ? p.p8 : 0, in.pl ? p.chmax : 0, pl.rt * pl.ct};
     for (int i = 0; i < 16; ++i) out16[i] = v[i];
-    return true;
 }
 
-// Returns RH_OK with *used = false when the geometry does not fit this path.  ws must hold rh_wgrad_x6_workspace bytes.
-// rsum_out != null: also the row sums of R over (batch, position) -- the bias gradient when R = dy -- from the same pass
-// left_z != null and the K range was split: the weight partials stay UNREDUCED in ws ([Z][M][C*T], *left_z = Z) for a caller
-// that folds the reduction into its next pass (conv_wgrad.hip: reduce_wn_bwd_kernel); the bias partials are reduced here.
-int rh_wgrad_x6_launch(const WgradP& w, float* dw, float* rsum_out, void* ws, hipStream_t stream, bool* used, int* left_z,
-                       const unsigned* r_range, const unsigned* s_range) {
-    *used = false;
-    if (left_z) *left_z = 0;
-    Wx6P p;
-    Wx6Plan pl{};
-    if (!plan_wx6(w, &p, &pl, r_range, s_range)) return RH_OK;
+// ws must hold planned.ws_bytes.  The weight partials of a split K range stay UNREDUCED in ws ([Z][M][C*T]) for the caller's
+// reduction tail (conv_wgrad.hip: finish_dw); the row-sum (bias) partials behind them are reduced here.
+int rh_wgrad_x6_launch(const RhWx6Planned& planned, float* dw, float* rsum_out, void* ws, hipStream_t stream) {
+    Wx6P p = wx6_planned(planned).p;
+    const Wx6Plan& pl = wx6_planned(planned).pl;
     p.out = pl.Z > 1 ? (float*)ws : dw;
-    float* const rs_part = (float*)ws + (pl.Z > 1 ? (long)pl.Z * w.M * w.C * w.T : 0);
+    float* const rs_part = (float*)ws + (pl.Z > 1 ? (long)pl.Z * p.M * p.C * p.T : 0);
     p.rsum = rsum_out ? (pl.Z > 1 ? rs_part : rsum_out) : nullptr;
     const dim3 grid = pl.nw > 0 ? dim3(pl.Z) : dim3(pl.ct, pl.rt, pl.Z);
     wx6_instance(wx6_inst_of(p, pl))(grid, pl.nw > 0 ? 64 * pl.nw : 256, pl.lds, stream, p);
     if (int e = rh_check_launch("conv1d_bwd_weight_x6")) return e;
-    *used = true;
-    if (pl.Z > 1) {
-        if (left_z) *left_z = pl.Z;
-        else if (int e = rh_reduce_partials_launch((const float*)ws, dw, (long)w.M * w.C * w.T, pl.Z, stream, "conv1d_bwd_weight_reduce")) return e;
-        if (rsum_out) return rh_reduce_partials_launch(rs_part, rsum_out, w.M, pl.Z, stream, "conv1d_bwd_bias_reduce");
-    }
+    if (pl.Z > 1 && rsum_out) return rh_reduce_partials_launch(rs_part, rsum_out, p.M, pl.Z, stream, "conv1d_bwd_bias_reduce");
     return RH_OK;
 }
-

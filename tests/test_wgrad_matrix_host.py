@@ -2,7 +2,8 @@
 names (a change that re-routes a geometry fails here and must update the table), every one of the 48 x6 instances and every
 reachable f32-input instance has a row, and every listed edge occurs for every kernel kind it exists for.  No GPU:
 rh_conv1d_bwd_weight_instance_info is a pure function of the descriptor, the alignment flags and the per-call switches, answered
-by the planner and the instance selection the launch itself runs.  tests/test_gpu_wgrad_matrix.py runs the same rows on the GPU."""
+by route_wgrad1 (csrc/conv_wgrad.hip), the function the launch itself goes through; the scratch query is a caller of it too.
+tests/test_gpu_wgrad_matrix.py runs the same rows on the GPU."""
 import ctypes as C
 import os
 
@@ -89,6 +90,24 @@ def test_out_of_scope_families_are_reported(L):
         assert fam in (0, 1)
         with W.call_env(r):
             assert W.instance_info(L, r)[0] <= fam       # family 1 geometries fall to 0 unarmed / switched off, never the reverse
+
+
+@pytest.mark.parametrize("armed", (True, False), ids=("armed", "unarmed"))
+def test_workspace_query_covers_the_routed_launch(L, armed):
+    """rh_conv1d_workspace_bytes (one answer, asked before the caller knows whether the call will be armed) is at least what the
+    launch the route chooses demands: the bias scratch, Z > 1 slices of M x C x T partials behind it, and for family 1 the Z x M
+    row-sum partials.  The formulas are restated here from W.gemm, not read from the library."""
+    for r in W.ROWS:
+        row = r._replace(armed=armed)
+        info, g = W.instance_info(L, row), W.gemm(row.geo)
+        assert info[0] in (0, 1), row.name
+        Z = info[7]
+        demand = int(L.lib.rh_act_bwd_bias_workspace_bytes(row.geo[2]))
+        if Z > 1:
+            demand += Z * g["M"] * g["C"] * g["T"] * 4
+        if info[0] == 1:
+            demand += Z * g["M"] * 4
+        assert W.workspace_bytes(L, row) >= demand, (row.name, armed, W.workspace_bytes(L, row), demand)
 
 
 def _ledger(L):

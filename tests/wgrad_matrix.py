@@ -5,7 +5,7 @@ no GPU).  The counterpart of tests/x6_matrix.py for the forward / data-gradient 
 48 x6 instances: ``wgrad_x6_kernel<TM, WM, 4 / WM, AV, PART, PL>`` (40: six (tm, wm) x AV x PART, x PL for tm >= 2) and
 ``wgrad_x6_wide_kernel<NW, PL>`` (8); the f32-input family adds ``wgrad_dma_kernel<.., RLEAKY, SLEAKY>`` (five tile shapes x three
 activation modes x vec / non-vec staging = 30) and ``wgrad_kernel`` (five shapes, snake layers).  ``rh_conv1d_bwd_weight_instance_info``
-answers "which one" on the host from the planner and the instance selection the launch itself runs.  ``ROWS`` was found by
+answers "which one" on the host from route_wgrad1 (conv_wgrad.hip), the function the launch itself goes through.  ``ROWS`` was found by
 tests/wgrad_matrix_search.py (a greedy cover over random small geometries); tests/test_wgrad_matrix_host.py proves the coverage from
 the diagnostic alone and tests/test_gpu_wgrad_matrix.py runs every row against f64.
 
@@ -32,7 +32,7 @@ PER_CALL = ("RH_WGRAD_X6", "RH_WGRAD_X6_PLANES", "RH_WGRAD_X6_WIDE", "RH_WGRAD_X
 ONCE_PER_PROCESS = ("RH_WGRAD_X6_TM", "RH_WGRAD_X6_ALL", "RH_WGRAD_RK", "RH_WGRAD_RK_INNER", "RH_WGRAD_BLOCKS", "RH_WGRAD_MINCHUNKS",
                     "RH_WGRAD_NOVEC")
 KINDS = ("4-wave", "4-wave PL", "wide", "wide PL", "dma vec", "dma non-vec")
-F0_SHAPES = ((32, 256), (64, 128), (96, 96), (96, 128), (128, 128))        # conv_wgrad.hip: w_shape
+F0_SHAPES = ((32, 256), (64, 128), (96, 96), (96, 128), (128, 128))        # conv_wgrad.hip: w_shape, and the ladder in route_wgrad1
 
 
 class Env:
