@@ -505,6 +505,22 @@ int rh_feed_batch_post_i16_f32(const int16_t* pcm, int64_t pcm_samples, const rh
                                double max_gain_db, int32_t derivative, void* workspace, int64_t workspace_bytes, float* out,
                                rh_stream_t stream);
 
+/* FrequencyMasking (rave/transforms.py:180-195) on finished float32 rows, one launch: row r of x (n_rows, n_signal) with
+ * bands[2r] = first_bin, bands[2r + 1] = n_bins loses the bins [first_bin, first_bin + n_bins) of
+ * scipy.signal.stft(x, nperseg = 4096) -- periodic Hann w, hop 2048, boundary = 'zeros', 2049 bins -- and is rebuilt by
+ * scipy.signal.istft.  Computed as x minus the band component: with xpad_t the frame t of the zero-padded row (the samples
+ * [2048 (t - 1), 2048 (t + 1)) of x), B the indicator of the band and h_t = irfft(B . rfft(w . xpad_t)),
+ *   y[2048 b + j] = x[2048 b + j] - (w[j] h_{b+1}[j] + w[j + 2048] h_b[j + 2048]) / (w[j]^2 + w[j + 2048]^2),   0 <= j < 2048
+ * in float32 (the 4096-point real transforms run as 2048-point complex ones in LDS); every sample has one writer and one order
+ * of operations: the same bits on every run.  A row with n_bins <= 0 is copied bit for bit (the reference returns such an item
+ * itself); a band is clamped to the bins 0..2047 (the reference never masks the Nyquist bin).  `bands` is device memory and is
+ * not checked here: the caller validates its draws.  twiddle: e^{-2 pi i k / 4096}, k < 4096, interleaved re, im, 8-byte
+ * aligned (the table of rh_stft_loss_fwd_f32 for n_fft = 4096).  x and y must not overlap.
+ * Checked on the host, RH_ERR_INVALID and no launch otherwise: null pointers, n_rows <= 0, n_signal < 4096 or not a multiple
+ * of 2048 (lengths scipy would pad or shorten nperseg for), a misaligned table, overlapping x and y. */
+int rh_feed_freq_mask_f32(const float* x, float* y, const int32_t* bands, int32_t n_rows, int32_t n_signal,
+                          const float* twiddle, rh_stream_t stream);
+
 /* ---- spectral distance ("next" item #1 of SURVEY.md section 8f, beside the hot path) ------------- */
 
 /* STFT framing of torchaudio.transforms.Spectrogram(center=True, pad_mode="reflect") as used by

@@ -1,7 +1,7 @@
-// The in-LDS complex FFT shared by stft_loss.hip and mel.hip (N = 128 ... 2048; Stockham autosort, radix 8 + one radix 2 / 4
-// pass, N / 8 threads per transform, 256 / (N / 8) transforms per workgroup side by side), the reflect index of a centred
-// frame and the power-of-two equaliser of a frame pair.  Included INSIDE the including file's anonymous namespace, after
-// common.hpp; see the header of stft_loss.hip for the scheme.
+// The in-LDS complex FFT shared by stft_loss.hip, mel.hip and feed_mask.hip (N = 128 ... 2048; Stockham autosort, radix 8 +
+// one radix 2 / 4 pass, N / 8 threads per transform, 256 / (N / 8) transforms per workgroup side by side), the reflect index
+// of a centred frame and the power-of-two equaliser of a frame pair.  Included INSIDE the including file's anonymous namespace,
+// after common.hpp; see the header of stft_loss.hip for the scheme.
 
 typedef float c32 __attribute__((ext_vector_type(2)));       // complex as a packed pair: adds / twiddle products are v_pk_* ops
 
@@ -75,18 +75,21 @@ struct Fft {
         c32 a[7];            // pass NS = 8
         c32 b[MID2 ? 7 : 1]; // pass NS = 64 (1024 / 2048 only)
         c32 f[NTF];          // final pass
+        // `tw` holds e^{-2 pi i k / (S N)}, k < S N: S = 1 is the transform's own table, S = 2 the table of a real transform of
+        // 2 N points packed into this one (feed_mask.hip), whose even entries are this transform's
+        template <int S = 1>
         __device__ __forceinline__ void init(int t, const c32* __restrict__ tw) {
 #pragma unroll
-            for (int r = 1; r < 8; ++r) a[r - 1] = tw[r * (t & 7) * (N / 64)];
+            for (int r = 1; r < 8; ++r) a[r - 1] = tw[S * r * (t & 7) * (N / 64)];
             if (MID2) {
 #pragma unroll
-                for (int r = 1; r < 8; ++r) b[r - 1] = tw[r * (t & 63) * (N / 512)];
+                for (int r = 1; r < 8; ++r) b[r - 1] = tw[S * r * (t & 63) * (N / 512)];
             }
 #pragma unroll
             for (int u = 0; u < 8 / RF; ++u) {
                 const int k = (t + u * TPF) & (NSL - 1);
 #pragma unroll
-                for (int r = 1; r < RF; ++r) f[u * (RF - 1) + r - 1] = tw[r * k * (N / (NSL * RF))];
+                for (int r = 1; r < RF; ++r) f[u * (RF - 1) + r - 1] = tw[S * r * k * (N / (NSL * RF))];
             }
         }
     };

@@ -22,9 +22,18 @@ gain per item from the peak over all its channels, capped at ``max_gain_db`` = 3
 float64 rows and one peak per row in a workspace cached on the feed, a second kernel applies gain and difference in float64 and
 rounds once to float32.
 
-Not built: ``Resample`` (a dataset stored at another rate than ``sr``: torchaudio.functional.resample, rave/dataset.py:238-239),
-``Compress`` / ``RandomCompress`` (sox ``compand`` through torchaudio, rave/transforms.py:114-145) and ``FrequencyMasking``
-(commented out in the only config that names it).
+``freq_mask=prob`` adds ``FrequencyMasking(prob, max_size)`` (rave/transforms.py:180-195; named, commented out, in
+configs/v2_with_augs.gin and reachable through ``dataset.get_dataset.augmentations``): per item, with probability ``prob``, a band
+of ``randrange(1, max_size)`` bins at ``randrange(0, 2049 - mask_size)`` is zeroed in scipy.signal.stft(x, nperseg=4096) and the
+item rebuilt by scipy.signal.istft.  It is a launch of its own behind the chain (rh_feed_freq_mask_f32, csrc/feed_mask.hip): the
+chain writes a float32 buffer cached on the feed, the mask kernel writes the batch; a batch in which no item is masked takes
+neither.  The reference masks its float64 item before the final float32 rounding, and RandomMute runs after the mask or before
+it, in config order; muting multiplies by 0 or 1 and commutes with the (linear) mask, so masking the chain's float32 output is the
+same transform up to one float32 rounding of the mask's input.  ``n_signal`` must be a multiple of 2048 of at least 4096: for any
+other length scipy pads the item (10000 samples become 10240) or shortens the window, and the feed refuses.
+
+Not built: ``Resample`` (a dataset stored at another rate than ``sr``: torchaudio.functional.resample, rave/dataset.py:238-239)
+and ``Compress`` / ``RandomCompress`` (sox ``compand`` through torchaudio, rave/transforms.py:114-145).
 """
 from __future__ import annotations
 
@@ -137,6 +146,33 @@ def draw_batch(rng: np.random.Generator, n_items: int, length: int, batch: int, 
     return items, in_points, angles, ratios
 
 
+MASK_BINS = 2048          # FrequencyMasking: bins a band can hold (the 2049 of nperseg = 4096 without Nyquist) = the hop
+
+
+def draw_bands(rng: np.random.Generator, batch: int, prob: float, max_size: int):
+    """FrequencyMasking's draws (rave/transforms.py:187-191) for one minibatch: per item None (random() >= prob) or
+    (freq_idx, mask_size), mask_size = randrange(1, max_size), freq_idx = randrange(0, 2049 - mask_size)."""
+    bands = [None] * batch
+    for b in range(batch):
+        if rng.random() < prob:
+            mask_size = int(rng.integers(1, max_size))
+            bands[b] = (int(rng.integers(0, MASK_BINS + 1 - mask_size)), mask_size)
+    return bands
+
+
+def check_bands(bands, batch: int):
+    """The injected or drawn bands of ``sample``: one (freq_idx, mask_size) or None per item; None when no item is masked."""
+    if bands is None:
+        return None
+    if len(bands) != batch:
+        raise RuntimeError(f"GpuBatchFeed: {len(bands)} bands for a batch of {batch}")
+    for b, band in enumerate(bands):
+        if band is not None and not (len(band) == 2 and band[1] >= 1 and band[0] >= 0 and band[0] + band[1] <= MASK_BINS):
+            raise RuntimeError(f"GpuBatchFeed: item {b}: band {tuple(band)} is not (freq_idx >= 0, mask_size >= 1) inside the "
+                               f"{MASK_BINS} bins below Nyquist")
+    return bands if any(band is not None for band in bands) else None
+
+
 def check_max_gain_db(max_gain_db) -> float:
     """The gain cap of normalize_signal (rave/dataset.py:196) as a finite float; anything else is an error."""
     if isinstance(max_gain_db, bool) or not isinstance(max_gain_db, (int, float, np.integer, np.floating)) \
@@ -155,13 +191,22 @@ class GpuBatchFeed:
     """``pcm``: int16 tensor (n_items, n_channels, length) on the GPU.  ``sample`` returns a (B, n_channels, n_signal)
     float32 minibatch ready for ``RAVE.training_step``.  ``rand_pitch=(lo, hi)``: RandomPitch(n_signal, [lo, hi], max_factor,
     prob=p_pitch) in front of the crop; ``p_mute``: RandomMute(p_mute) at the end of the chain; ``normalize`` / ``derivative``:
-    normalize_signal(x, max_gain_db) and the derivator between Dequantize and RandomMute (module docstring)."""
+    normalize_signal(x, max_gain_db) and the derivator between Dequantize and RandomMute; ``freq_mask``: FrequencyMasking(freq_mask,
+    freq_mask_max_size) on the finished chain, None = off (module docstring)."""
 
     def __init__(self, pcm: torch.Tensor, sr: int = 44100, seed: int = 0, p_mangle: float = .8, bit_depth: int = 16,
                  rand_pitch: Optional[Sequence[float]] = None, p_pitch: float = .5, max_factor: int = 20, p_mute: float = 0.,
-                 normalize: bool = False, derivative: bool = False, max_gain_db: float = 30.):
+                 normalize: bool = False, derivative: bool = False, max_gain_db: float = 30.,
+                 freq_mask: Optional[float] = None, freq_mask_max_size: int = 80):
         self.normalize, self.derivative, self.max_gain_db = bool(normalize), bool(derivative), check_max_gain_db(max_gain_db)
         self.workspace = None
+        if freq_mask is not None and not 0. <= freq_mask <= 1.:
+            raise RuntimeError("GpuBatchFeed: freq_mask must be None or a probability between 0 and 1")
+        if not 2 <= freq_mask_max_size <= MASK_BINS + 1:
+            raise RuntimeError(f"GpuBatchFeed: freq_mask_max_size must be 2..{MASK_BINS + 1} (mask_size = randrange(1, max_size) bins "
+                               f"of the {MASK_BINS} below Nyquist)")
+        self.freq_mask, self.freq_mask_max_size = freq_mask, int(freq_mask_max_size)
+        self.mask_input = None                      # the chain's output when a batch is masked: float32, cached like ``workspace``
         if pcm.dtype != torch.int16 or pcm.dim() != 3 or not pcm.is_cuda:
             raise RuntimeError("GpuBatchFeed: pcm must be an int16 (items, channels, length) tensor on the GPU")
         if not 0. <= p_mute <= 1.:
@@ -198,13 +243,26 @@ class GpuBatchFeed:
                                f"{self.pitch.shortest(length)} samples, fewer than n_signal = {n_signal}")
         return draw_batch(self.rng, n_items, length, batch, n_signal, self.sr, self.p_mangle, self.pitch)
 
-    def sample(self, batch: int, n_signal: int, draws=None, noise: Optional[torch.Tensor] = None, mute=None) -> torch.Tensor:
+    def sample(self, batch: int, n_signal: int, draws=None, noise: Optional[torch.Tensor] = None, mute=None,
+               bands=None) -> torch.Tensor:
         """``draws``: (items, in_points, angles) or (items, in_points, angles, ratios), ``ratios[b]`` = None or (up, down) and
-        ``in_points[b]`` then counted in resampled samples; ``mute``: optional mask, True = the item is silenced."""
-        if draws is None:
+        ``in_points[b]`` then counted in resampled samples; ``mute``: optional mask, True = the item is silenced; ``bands``
+        (with ``freq_mask``): per item None or (freq_idx, mask_size).  Like ``mute``, the bands are drawn only when the
+        ``draws`` are; they are drawn last, and only with ``freq_mask`` set: a feed without it consumes its generator exactly as
+        before."""
+        if self.freq_mask is None and bands is not None:
+            raise RuntimeError("GpuBatchFeed: bands given to a feed built without freq_mask")
+        if self.freq_mask is not None and (n_signal < 2 * MASK_BINS or n_signal % MASK_BINS):
+            raise RuntimeError(f"GpuBatchFeed: freq_mask needs n_signal to be a multiple of {MASK_BINS} of at least {2 * MASK_BINS}, "
+                               f"not {n_signal} (scipy.signal.stft would pad the item or shorten its window)")
+        drawn = draws is None
+        if drawn:
             draws = self.draw(batch, n_signal)
             if mute is None and self.p_mute > 0:
                 mute = self.rng.random(batch) < self.p_mute
+        if self.freq_mask is not None and bands is None and drawn:
+            bands = draw_bands(self.rng, batch, self.freq_mask, self.freq_mask_max_size)
+        bands = check_bands(bands, batch)
         items, in_points, angles = draws[:3]
         ratios = draws[3] if len(draws) > 3 else None
         n_items, n_ch, length = self.pcm.shape
@@ -214,6 +272,11 @@ class GpuBatchFeed:
             noise = torch.rand(rows, n_signal, device=dev, generator=self.gen)
         noise = noise.to(dev, torch.float32).contiguous()
         out = torch.empty(batch, n_ch, n_signal, device=dev, dtype=torch.float32)
+        dst = out                                   # where the chain writes: the batch itself unless a mask launch follows
+        if bands is not None:
+            if self.mask_input is None or self.mask_input.numel() < out.numel():     # regrown only when rows x n_signal grows
+                self.mask_input = torch.empty(out.numel(), device=dev, dtype=torch.float32)
+            dst = self.mask_input
         pitched = ratios is not None and any(r is not None for r in ratios)
         muted = mute is not None and any(mute)
         post = self.normalize or self.derivative
@@ -230,8 +293,8 @@ class GpuBatchFeed:
             off_d = torch.from_numpy(off).to(dev)
             coef_d = torch.from_numpy(coef).to(dev)
             L.check(L.lib.rh_feed_batch_i16_f32(L.ptr(self.pcm), L.ptr(off_d), L.ptr(coef_d), L.ptr(noise), rows, n_signal,
-                                                self.bit_depth, L.ptr(out), L.stream()), "feed_batch")
-            return out
+                                                self.bit_depth, L.ptr(dst), L.stream()), "feed_batch")
+            return self._mask(dst, out, bands)
         table = np.zeros(rows, dtype=ROW_DTYPE)
         table["coef"] = np.nan
         table["length"] = length
@@ -260,12 +323,28 @@ class GpuBatchFeed:
             L.check(L.lib.rh_feed_batch_post_i16_f32(L.ptr(self.pcm), self.pcm.numel(), table.ctypes.data, L.ptr(table_d),
                                                      L.ptr(self.taps), n_taps, L.ptr(noise), rows, n_signal, self.bit_depth,
                                                      n_ch, int(self.normalize), self.max_gain_db, int(self.derivative),
-                                                     L.ptr(self.workspace), self.workspace.numel() * 8, L.ptr(out), L.stream()),
+                                                     L.ptr(self.workspace), self.workspace.numel() * 8, L.ptr(dst), L.stream()),
                     "feed_batch_post")
-            return out
+            return self._mask(dst, out, bands)
         L.check(L.lib.rh_feed_batch_pitch_i16_f32(L.ptr(self.pcm), self.pcm.numel(), table.ctypes.data, L.ptr(table_d),
                                                   L.ptr(self.taps), n_taps, L.ptr(noise), rows, n_signal, self.bit_depth,
-                                                  L.ptr(out), L.stream()), "feed_batch_pitch")
+                                                  L.ptr(dst), L.stream()), "feed_batch_pitch")
+        return self._mask(dst, out, bands)
+
+    def _mask(self, chain_out: torch.Tensor, out: torch.Tensor, bands) -> torch.Tensor:
+        """FrequencyMasking of the finished chain: ``chain_out`` (the cached buffer) -> ``out``, every channel of an item with the
+        item's band; nothing to do (``chain_out`` is ``out``) when no item of the batch is masked."""
+        if bands is None:
+            return out
+        from .ops import _twiddle
+        batch, n_ch, n_signal = out.shape
+        table = np.zeros((batch, n_ch, 2), dtype=np.int32)                             # rows x {first_bin, n_bins}; 0 bins = copy
+        for b, band in enumerate(bands):
+            if band is not None:
+                table[b] = (int(band[0]), int(band[1]))
+        table_d = torch.from_numpy(table).to(out.device)
+        L.check(L.lib.rh_feed_freq_mask_f32(L.ptr(chain_out), L.ptr(out), L.ptr(table_d), batch * n_ch, n_signal,
+                                            L.ptr(_twiddle(2 * MASK_BINS, out.device)), L.stream()), "feed_freq_mask")
         return out
 
     def _tap_offset(self, ratio) -> int:

@@ -1,8 +1,9 @@
 """Throughput of the GPU data feed (rave_amd/data.py): batches of 32 x 65536 from 64 resident items.
 ``--rand-pitch lo,hi`` adds a leg with RandomPitch on (about half the items resampled), ``--post`` a leg with ``normalize``
-and ``derivative`` on (rh_feed_batch_post_i16_f32: the chain kernel plus the gain / difference kernel), ``--step`` the replayed
-v2 training step (bench.py's default workload) the feed has to hide under on a side stream -- all timed in the same process,
-with HIP events, in alternating windows."""
+and ``derivative`` on (rh_feed_batch_post_i16_f32: the chain kernel plus the gain / difference kernel), ``--freq_mask P`` two
+legs with FrequencyMasking on (rh_feed_freq_mask_f32 behind the chain: every item masked, and a share P of them), ``--step`` the
+replayed v2 training step (bench.py's default workload) the feed has to hide under on a side stream -- all timed in the same
+process, with HIP events, in alternating windows.  The "feed" leg is the chain launch alone."""
 import argparse
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -13,6 +14,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--rand-pitch", default=None, help="lo,hi: also time the feed with RandomPitch in this range")
 ap.add_argument("--p-pitch", type=float, default=.5, help="share of the items that are resampled (reference: 0.5)")
 ap.add_argument("--post", action="store_true", help="also time the feed with normalize=True, derivative=True")
+ap.add_argument("--freq_mask", type=float, default=None, metavar="P",
+                help="also time the feed with FrequencyMasking: all items masked, and with probability P")
 ap.add_argument("--step", action="store_true", help="also time the replayed v2 training step at batch 32 x 65536")
 ap.add_argument("--reps", type=int, default=3, help="timed windows per leg, alternating between the legs")
 args = ap.parse_args()
@@ -25,6 +28,9 @@ if args.rand_pitch:
     legs.append((f"feed --rand-pitch {lo:g},{hi:g} (p = {args.p_pitch:g})", D.GpuBatchFeed(pcm, seed=0, rand_pitch=(lo, hi), p_pitch=args.p_pitch)))
 if args.post:
     legs.append(("feed normalize + derivative", D.GpuBatchFeed(pcm, seed=0, normalize=True, derivative=True)))
+if args.freq_mask is not None:
+    legs.append(("feed + freq_mask, all rows masked", D.GpuBatchFeed(pcm, seed=0, freq_mask=1.)))
+    legs.append((f"feed + freq_mask (p = {args.freq_mask:g})", D.GpuBatchFeed(pcm, seed=0, freq_mask=args.freq_mask)))
 
 
 class Step:
