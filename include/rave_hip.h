@@ -505,6 +505,35 @@ int rh_feed_batch_post_i16_f32(const int16_t* pcm, int64_t pcm_samples, const rh
                                double max_gain_db, int32_t derivative, void* workspace, int64_t workspace_bytes, float* out,
                                rh_stream_t stream);
 
+/* The chain of rh_feed_batch_post_i16_f32 with the Resample the reference puts right behind Dequantize when the stored
+ * dataset's rate differs from the run's (rave/dataset.py:238-239, rave/transforms.py:31-40:
+ * torchaudio.functional.resample(x.float(), orig_freq, new_freq) with its defaults -- sinc_interp_hann, lowpass_filter_width 6,
+ * rolloff .99 -- on the cropped item).  With o, n = orig_freq, new_freq over their gcd, width = ceil(6 o / (.99 min(o, n))),
+ * K = 2 width + o, h = res_taps, the float32 (n, K) table of torchaudio's _get_sinc_resample_kernel (rave_amd/data.py:
+ * sinc_resample_kernel), and v the float64 row behind Dequantize (rh_feed_batch_post_i16_f32):
+ *   y[r][q n + i] = float32(sum_{k < K} h[i][k] xpad[q o + k]),  xpad[m] = float32(v[r][m - width]) inside [0, n_signal), else 0,
+ *                   summed in float64 in ascending k                         q n + i < n_res = ceil(n n_signal / o)
+ * normalize / derivative then act on the rows y of n_res samples exactly as rh_feed_batch_post_i16_f32 describes for v, and
+ * `out` is (n_rows, n_res); a row with mute != 0 is all zeros and adds nothing to the peak.  The all-pass in `rows` keeps the
+ * dataset's rate; noise is (n_rows, n_signal).
+ * Two or three launches on `stream`: the chain kernel leaves v and its peaks in `workspace`, the resampling kernel writes `out`
+ * (both steps off) or y as doubles and max |y| per row into a second region of it, the kernel of the post entry point finishes.
+ * No atomics, one writer and one order of operations per sample: the same bits on every run.  `workspace`:
+ * rh_feed_resample_workspace_bytes bytes (negative: bad arguments), 8-byte aligned device memory owned by the caller.
+ * orig_freq == new_freq is rh_feed_batch_post_i16_f32 (same bits; res_taps, n_res_taps and width are not looked at, and the
+ * workspace is the one of that entry point).
+ * Checked on the host, RH_ERR_INVALID and no launch otherwise: everything rh_feed_batch_post_i16_f32 checks; orig_freq,
+ * new_freq >= 1; `width` and n_res_taps == n K against the expression above recomputed in double; K <= 8192 (kResSpan) and
+ * n <= 6144 (kResOut), what one pass of the kernel stages in LDS -- every pair of the rates 16000 .. 96000 in common use fits
+ * (largest K 694 at 96000 -> 22050, largest n 640 and largest table, 1.16 MB, at 22050 -> 32000); n_res and K inside int32; the size and alignment of the workspace. */
+int64_t rh_feed_resample_workspace_bytes(int32_t n_rows, int32_t n_signal, int32_t orig_freq, int32_t new_freq);
+int rh_feed_batch_resample_i16_f32(const int16_t* pcm, int64_t pcm_samples, const rh_feed_pitch_row* rows,
+                                   const rh_feed_pitch_row* rows_dev, const double* taps, int32_t n_taps, const float* noise,
+                                   int32_t n_rows, int32_t n_signal, int32_t bit_depth, int32_t n_channels, int32_t normalize,
+                                   double max_gain_db, int32_t derivative, int32_t orig_freq, int32_t new_freq,
+                                   const float* res_taps, int64_t n_res_taps, int32_t width, void* workspace,
+                                   int64_t workspace_bytes, float* out, rh_stream_t stream);
+
 /* FrequencyMasking (rave/transforms.py:180-195) on finished float32 rows, one launch: row r of x (n_rows, n_signal) with
  * bands[2r] = first_bin, bands[2r + 1] = n_bins loses the bins [first_bin, first_bin + n_bins) of
  * scipy.signal.stft(x, nperseg = 4096) -- periodic Hann w, hop 2048, boundary = 'zeros', 2049 bins -- and is rebuilt by

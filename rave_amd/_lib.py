@@ -125,6 +125,9 @@ def _load() -> C.CDLL:
         "rh_feed_batch_pitch_i16_f32": ([P, I64, P, P, P, I32, P, I32, I32, I32, P, P], C.c_int),
         "rh_feed_post_workspace_bytes": ([I32, I32], I64),
         "rh_feed_batch_post_i16_f32": ([P, I64, P, P, P, I32, P, I32, I32, I32, I32, I32, C.c_double, I32, P, I64, P, P], C.c_int),
+        "rh_feed_resample_workspace_bytes": ([I32, I32, I32, I32], I64),
+        "rh_feed_batch_resample_i16_f32": ([P, I64, P, P, P, I32, P, I32, I32, I32, I32, I32, C.c_double, I32, I32, I32, P, I64, I32,
+                                            P, I64, P, P], C.c_int),
         "rh_feed_freq_mask_f32": ([P, P, P, I32, I32, P, P], C.c_int),
         "rh_vq_loss_partials": ([I64], I64),
         "rh_vq_assign_f32": ([P, P, I64, I32, I32, P, P, P, P, P], C.c_int),

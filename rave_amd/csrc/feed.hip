@@ -221,6 +221,108 @@ __global__ __launch_bounds__(256) void feed_post_kernel(const double* __restrict
     }
 }
 
+// ---- Resample behind Dequantize (a dataset stored at another rate than the run's `sr`) ---------------------------------------
+//   Resample(sr_dataset, sr)          (transforms.py:31-40, dataset.py:238-239: torchaudio.functional.resample(x.float(), orig,
+//                                      new), sinc_interp_hann, lowpass_filter_width 6, rolloff .99, on the CROPPED item)
+// With o, n = orig, new over their gcd, width = ceil(6 o / (.99 min(o, n))), K = 2 width + o and the float32 table h (n, K) of
+// the host (rave_amd/data.py: sinc_resample_kernel), torchaudio's strided convolution written out:
+//   y[q n + i] = sum_{k < K} h[i][k] xpad[q o + k],   xpad[m] = float32(v[m - width]) inside [0, n_signal), 0 outside,
+//   q n + i < n_res = ceil(n n_signal / o)
+// Launched between feed_pitch_kernel<true>, which left the float64 rows v in the workspace, and feed_post_kernel.  A workgroup
+// per row, as in the chain kernel, in passes of `nq` frames q: the input span (nq - 1) o + K of a pass is staged in LDS as
+// float32 (the `.float()`; the pads are zeros and are never read from memory), work item w = i * nq + qr takes filter i at frame
+// qr, so the lanes of a wave share one or two filters -- their tap loads from the (up to 1.2 MB, L2-resident) table fall on the
+// same address and walk a cache line with k -- and differ in qr: their LDS reads are o apart, and the image is padded by one
+// word per 32 (res_pad) so that an o that is a multiple of 32 (160 / 147) does not put them all on one bank.  float32 tap times
+// float32 sample is exact in float64; the sum runs in float64 in ascending k and is rounded ONCE to float32 (what the
+// reference's float32 convolution returns, up to its own rounding).  The pass's outputs meet in LDS in output order and leave
+// with unit-stride scalar stores (`out` may be 4-byte aligned): kPost = false to `out`; kPost = true as doubles to the second
+// region of the workspace, with max |row| behind it, for feed_post_kernel on rows of n_res samples.  A muted row is not read.
+constexpr int kResSpan = 8192;      // input samples staged per pass: K <= kResSpan (checked by the host)
+constexpr int kResOut = 6144;       // outputs per pass: n <= kResOut (checked by the host)
+
+__host__ __device__ inline int res_pad(int m) { return m + (m >> 5); }
+
+template <bool kPost>
+__global__ __launch_bounds__(256) void feed_resample_kernel(const double* __restrict__ ws, const rh_feed_pitch_row* __restrict__ rows,
+                                                            const float* __restrict__ taps, int n_signal, int n_res, int o, int n,
+                                                            int K, int width, float* __restrict__ out, double* __restrict__ ws2,
+                                                            double* __restrict__ peaks2) {
+    __shared__ float span[kResSpan + kResSpan / 32 + 1];
+    __shared__ float ybuf[kResOut];
+    const int r = blockIdx.x;
+    if (rows[r].mute) {                         // the chain kernel left nothing for this row but the peak 0
+        if constexpr (kPost) {
+            if (threadIdx.x == 0) peaks2[r] = 0.0;
+        } else {
+            for (int i = threadIdx.x; i < n_res; i += 256) out[(long)r * n_res + i] = 0.f;
+        }
+        return;
+    }
+    [[maybe_unused]] double peak = 0.0;
+    const double* __restrict__ x = ws + (long)r * n_signal;
+    const int frames = (n_res + n - 1) / n;
+    const int qc = min((kResSpan - K) / o + 1, kResOut / n);           // frames per pass: span and outputs both fit
+    for (int q0 = 0; q0 < frames; q0 += qc) {
+        const int nq = min(qc, frames - q0);
+        const int cnt = (nq - 1) * o + K;
+        const int64_t m0 = (int64_t)q0 * o - width;                    // span[0] is v[m0]
+        for (int s = threadIdx.x; s < cnt; s += 256) {
+            const int64_t m = m0 + s;
+            span[res_pad(s)] = m >= 0 && m < n_signal ? (float)x[m] : 0.f;
+        }
+        __syncthreads();
+        for (int w = threadIdx.x; w < n * nq; w += 256) {
+            const int i = w / nq, qr = w - i * nq;
+            const float* __restrict__ h = taps + (long)i * K;
+            const int s0 = qr * o;
+            double acc = 0.0;
+            for (int k = 0; k < K; ++k) acc += (double)h[k] * (double)span[res_pad(s0 + k)];
+            ybuf[qr * n + i] = (float)acc;
+        }
+        __syncthreads();
+        const int64_t j0 = (int64_t)q0 * n;
+        const int len = (int)min((int64_t)nq * n, n_res - j0);         // the last frame is cut at n_res
+        for (int j = threadIdx.x; j < len; j += 256) {
+            const long at = (long)r * n_res + j0 + j;
+            const float v = ybuf[j];
+            if constexpr (kPost) {
+                ws2[at] = (double)v;
+                peak = fmax(peak, fabs((double)v));
+            } else {
+                out[at] = v;
+            }
+        }
+        // no barrier: the next pass writes ybuf only behind its own first barrier, and span only after every thread is past the one above
+    }
+    if constexpr (kPost) {                      // max is exact: any reduction order gives the same bits
+        __shared__ double red[256];
+        red[threadIdx.x] = peak;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if ((int)threadIdx.x < s) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + s]);
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) peaks2[r] = red[0];
+    }
+}
+
+// o, n, width, K and n_res of a rate pair, or false when a length leaves int32
+struct ResPlan { int o, n, width, K, n_res; };
+bool feed_resample_plan(int32_t orig_freq, int32_t new_freq, int32_t n_signal, ResPlan* p) {
+    const int g = feed_gcd(orig_freq, new_freq);
+    p->o = orig_freq / g;
+    p->n = new_freq / g;
+    const double width = std::ceil(6.0 * p->o / (std::min(p->o, p->n) * 0.99));       // the IEEE expression of the host table
+    const int64_t K = 2 * (int64_t)width + p->o;
+    const int64_t n_res = ((int64_t)p->n * n_signal + p->o - 1) / p->o;
+    if (K > 0x7fffffffll || n_res > 0x7fffffffll) return false;
+    p->width = (int)width;
+    p->K = (int)K;
+    p->n_res = (int)n_res;
+    return true;
+}
+
 // the checks of the pitched entry points on the host copy of the row table
 int feed_check_rows(const char* what, int64_t pcm_samples, const rh_feed_pitch_row* rows, const double* taps, int32_t n_taps,
                     int32_t n_rows, int32_t n_signal) {
@@ -307,4 +409,67 @@ extern "C" int rh_feed_batch_post_i16_f32(const int16_t* pcm, int64_t pcm_sample
     hipLaunchKernelGGL(feed_post_kernel, dim3(n_rows * tiles), dim3(256), 0, (hipStream_t)stream, (const double*)ws,
                        (const double*)peaks, rows_dev, n_signal, tiles, n_channels, normalize, max_gain_db, derivative, out);
     return rh_check_launch("feed_batch_post: normalize / derivative");
+}
+
+extern "C" int64_t rh_feed_resample_workspace_bytes(int32_t n_rows, int32_t n_signal, int32_t orig_freq, int32_t new_freq) {
+    if (n_rows < 0 || n_signal <= 0 || orig_freq < 1 || new_freq < 1) return -1;
+    const int64_t chain = rh_feed_post_workspace_bytes(n_rows, n_signal);
+    if (orig_freq == new_freq) return chain;
+    ResPlan p;
+    if (!feed_resample_plan(orig_freq, new_freq, n_signal, &p)) return -1;
+    return chain + rh_feed_post_workspace_bytes(n_rows, p.n_res);                // the chain's rows and peaks, then the resampled ones
+}
+
+extern "C" int rh_feed_batch_resample_i16_f32(const int16_t* pcm, int64_t pcm_samples, const rh_feed_pitch_row* rows,
+                                              const rh_feed_pitch_row* rows_dev, const double* taps, int32_t n_taps,
+                                              const float* noise, int32_t n_rows, int32_t n_signal, int32_t bit_depth,
+                                              int32_t n_channels, int32_t normalize, double max_gain_db, int32_t derivative,
+                                              int32_t orig_freq, int32_t new_freq, const float* res_taps, int64_t n_res_taps,
+                                              int32_t width, void* workspace, int64_t workspace_bytes, float* out,
+                                              rh_stream_t stream) {
+    RH_REQUIRE(orig_freq >= 1 && new_freq >= 1, RH_ERR_INVALID, "feed_batch_resample: rates %d -> %d", orig_freq, new_freq);
+    if (orig_freq == new_freq)                  // Resample returns its input: the feed without it, same bits
+        return rh_feed_batch_post_i16_f32(pcm, pcm_samples, rows, rows_dev, taps, n_taps, noise, n_rows, n_signal, bit_depth,
+                                          n_channels, normalize, max_gain_db, derivative, workspace, workspace_bytes, out, stream);
+    RH_REQUIRE(n_rows >= 0 && n_signal > 0 && bit_depth > 0 && bit_depth < 32 && pcm_samples >= 0 && n_taps >= 0, RH_ERR_INVALID,
+               "feed_batch_resample: bad sizes");
+    RH_REQUIRE(n_channels >= 1 && n_rows % n_channels == 0, RH_ERR_INVALID,
+               "feed_batch_resample: %d rows are not whole items of %d channels", n_rows, n_channels);
+    RH_REQUIRE(std::isfinite(max_gain_db), RH_ERR_INVALID, "feed_batch_resample: max_gain_db is not finite");
+    ResPlan p;
+    RH_REQUIRE(feed_resample_plan(orig_freq, new_freq, n_signal, &p), RH_ERR_INVALID,
+               "feed_batch_resample: %d samples at %d -> %d leave int32", n_signal, orig_freq, new_freq);
+    RH_REQUIRE(width == p.width, RH_ERR_INVALID, "feed_batch_resample: width %d, but %d -> %d has ceil(6 o / (.99 min(o, n))) = %d",
+               width, orig_freq, new_freq, p.width);
+    RH_REQUIRE(n_res_taps == (int64_t)p.n * p.K, RH_ERR_INVALID, "feed_batch_resample: table of %lld taps, %d x %d needed",
+               (long long)n_res_taps, p.n, p.K);
+    RH_REQUIRE(p.K <= kResSpan, RH_ERR_INVALID, "feed_batch_resample: %d taps per filter exceed kResSpan = %d", p.K, kResSpan);
+    RH_REQUIRE(p.n <= kResOut, RH_ERR_INVALID, "feed_batch_resample: %d filters exceed kResOut = %d", p.n, kResOut);
+    if (n_rows == 0) return RH_OK;
+    RH_REQUIRE(pcm && rows && rows_dev && noise && res_taps && out, RH_ERR_INVALID, "feed_batch_resample: null pointer");
+    const int64_t need = rh_feed_resample_workspace_bytes(n_rows, n_signal, orig_freq, new_freq);
+    RH_REQUIRE(workspace && workspace_bytes >= need, RH_ERR_INVALID, "feed_batch_resample: workspace of %lld bytes, %lld needed",
+               (long long)workspace_bytes, (long long)need);
+    RH_REQUIRE((uintptr_t)workspace % 8 == 0, RH_ERR_INVALID, "feed_batch_resample: workspace is not 8-byte aligned");
+    const int tiles = (p.n_res + kPostTile - 1) / kPostTile;
+    RH_REQUIRE((int64_t)n_rows * tiles <= 0x7fffffffll, RH_ERR_INVALID, "feed_batch_resample: too many tiles for one launch");
+    if (const int rc = feed_check_rows("feed_batch_resample", pcm_samples, rows, taps, n_taps, n_rows, n_signal)) return rc;
+    double* ws = (double*)workspace;
+    double* peaks = ws + (int64_t)n_rows * n_signal;
+    double* ws2 = peaks + n_rows;
+    double* peaks2 = ws2 + (int64_t)n_rows * p.n_res;
+    hipLaunchKernelGGL(feed_pitch_kernel<true>, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, pcm, rows_dev, taps, noise,
+                       n_signal, 1.0 / (double)(1ll << bit_depth), out, ws, peaks);
+    if (const int rc = rh_check_launch("feed_batch_resample")) return rc;
+    if (!normalize && !derivative) {
+        hipLaunchKernelGGL(feed_resample_kernel<false>, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, (const double*)ws, rows_dev,
+                           res_taps, n_signal, p.n_res, p.o, p.n, p.K, p.width, out, (double*)nullptr, (double*)nullptr);
+        return rh_check_launch("feed_batch_resample: resample");
+    }
+    hipLaunchKernelGGL(feed_resample_kernel<true>, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, (const double*)ws, rows_dev,
+                       res_taps, n_signal, p.n_res, p.o, p.n, p.K, p.width, out, ws2, peaks2);
+    if (const int rc = rh_check_launch("feed_batch_resample: resample")) return rc;
+    hipLaunchKernelGGL(feed_post_kernel, dim3(n_rows * tiles), dim3(256), 0, (hipStream_t)stream, (const double*)ws2,
+                       (const double*)peaks2, rows_dev, p.n_res, tiles, n_channels, normalize, max_gain_db, derivative, out);
+    return rh_check_launch("feed_batch_resample: normalize / derivative");
 }

@@ -32,8 +32,18 @@ it, in config order; muting multiplies by 0 or 1 and commutes with the (linear) 
 same transform up to one float32 rounding of the mask's input.  ``n_signal`` must be a multiple of 2048 of at least 4096: for any
 other length scipy pads the item (10000 samples become 10240) or shortens the window, and the feed refuses.
 
-Not built: ``Resample`` (a dataset stored at another rate than ``sr``: torchaudio.functional.resample, rave/dataset.py:238-239)
-and ``Compress`` / ``RandomCompress`` (sox ``compand`` through torchaudio, rave/transforms.py:114-145).
+``resample_to=rate`` adds the ``Resample(sr_dataset, sr)`` that ``get_dataset`` appends right behind Dequantize when the stored
+dataset's ``metadata.yaml`` rate (``load_lmdb_dataset``: ``info["sr"]``, the ``sr`` of this class) differs from the run's
+(rave/dataset.py:238-239, rave/transforms.py:31-40: torchaudio.functional.resample(x.float(), orig, new) with its defaults).
+torchaudio's filter table is built on the host in float32 as torchaudio builds it (``sinc_resample_kernel``) and kept on the
+device; a launch between the chain kernel and the normalize / derivative kernel (rh_feed_batch_resample_i16_f32) applies it to
+the cropped rows, float32 taps times float32 samples summed in float64 and rounded once.  ``sample`` then returns
+``sinc_resampled_length(n_signal, sr, resample_to)`` samples per row, everything behind Resample (normalize, derivative,
+RandomMute, ``freq_mask`` and its length rule) works on those, and the all-pass keeps the dataset's rate, as in the reference.
+Resample takes no random draws.
+
+Not built: ``Compress`` / ``RandomCompress`` (sox ``compand`` through torchaudio, rave/transforms.py:114-145): sox can neither
+be run here nor modelled against anything.
 """
 from __future__ import annotations
 
@@ -89,6 +99,33 @@ def resample_taps(up: int, down: int) -> np.ndarray:
 
 def resampled_length(length: int, up: int, down: int) -> int:
     return -(-length * up // down)
+
+
+def sinc_resample_kernel(orig: int, new: int):
+    """The filters of torchaudio.functional.resample(x.float(), orig, new) with its defaults (torchaudio 0.12 - 2.x,
+    _get_sinc_resample_kernel: sinc_interp_hann, lowpass_filter_width 6, rolloff .99), built as it builds them, with torch CPU ops
+    in float32 (the dtype of the waveform): (table, width), ``table`` float32 (n, K), n = new / gcd, K = 2 width + orig / gcd."""
+    g = math.gcd(orig, new)
+    o, n = orig // g, new // g
+    base = min(o, n) * 0.99
+    width = math.ceil(6 * o / base)
+    idx = torch.arange(-width, width + o, dtype=torch.float32)[None, None] / o
+    t = torch.arange(0, -n, -1, dtype=torch.float32)[:, None, None] / n + idx
+    t *= base
+    t.clamp_(-6, 6)
+    window = torch.cos(t * math.pi / 6 / 2) ** 2
+    t *= math.pi
+    kernels = torch.where(t == 0, torch.tensor(1.0).to(t), t.sin() / t) * (window * (base / o))
+    return kernels.reshape(n, 2 * width + o), width
+
+
+def sinc_resampled_length(length: int, orig: int, new: int) -> int:
+    """Samples torchaudio.functional.resample keeps of ``length``: ceil(new * length / orig)."""
+    return -(-new * length // orig)
+
+
+# mirror of kResSpan / kResOut (csrc/feed.hip): what one pass of the resampling kernel stages in LDS
+RES_SPAN, RES_OUT = 8192, 6144
 
 
 class PitchTable:
@@ -173,6 +210,23 @@ def check_bands(bands, batch: int):
     return bands if any(band is not None for band in bands) else None
 
 
+def check_resample(orig, new):
+    """(table, width) of ``sinc_resample_kernel`` for Resample(orig, new), or an error: rates that are not positive integers, or
+    a ratio whose filters one pass of the kernel cannot stage (K taps per filter <= kResSpan, n filters <= kResOut)."""
+    for rate in (orig, new):
+        if isinstance(rate, bool) or not isinstance(rate, (int, np.integer)) or not 1 <= rate < 2 ** 31:
+            raise RuntimeError(f"GpuBatchFeed: Resample needs sr and resample_to as positive integer rates, not {orig!r} -> {new!r}")
+    orig, new = int(orig), int(new)
+    g = math.gcd(orig, new)
+    o, n = orig // g, new // g
+    k = 2 * math.ceil(6 * o / (min(o, n) * 0.99)) + o
+    if k > RES_SPAN:
+        raise RuntimeError(f"GpuBatchFeed: Resample {orig} -> {new} ({o}/{n}) needs {k} taps per filter, more than kResSpan = {RES_SPAN}")
+    if n > RES_OUT:
+        raise RuntimeError(f"GpuBatchFeed: Resample {orig} -> {new} ({o}/{n}) needs {n} filters, more than kResOut = {RES_OUT}")
+    return sinc_resample_kernel(orig, new)
+
+
 def check_max_gain_db(max_gain_db) -> float:
     """The gain cap of normalize_signal (rave/dataset.py:196) as a finite float; anything else is an error."""
     if isinstance(max_gain_db, bool) or not isinstance(max_gain_db, (int, float, np.integer, np.floating)) \
@@ -192,12 +246,13 @@ class GpuBatchFeed:
     float32 minibatch ready for ``RAVE.training_step``.  ``rand_pitch=(lo, hi)``: RandomPitch(n_signal, [lo, hi], max_factor,
     prob=p_pitch) in front of the crop; ``p_mute``: RandomMute(p_mute) at the end of the chain; ``normalize`` / ``derivative``:
     normalize_signal(x, max_gain_db) and the derivator between Dequantize and RandomMute; ``freq_mask``: FrequencyMasking(freq_mask,
-    freq_mask_max_size) on the finished chain, None = off (module docstring)."""
+    freq_mask_max_size) on the finished chain, None = off; ``resample_to``: Resample(sr, resample_to) behind Dequantize, None or
+    ``sr`` itself = off, otherwise ``sample`` returns (B, n_channels, ceil(resample_to n_signal / sr)) (module docstring)."""
 
     def __init__(self, pcm: torch.Tensor, sr: int = 44100, seed: int = 0, p_mangle: float = .8, bit_depth: int = 16,
                  rand_pitch: Optional[Sequence[float]] = None, p_pitch: float = .5, max_factor: int = 20, p_mute: float = 0.,
                  normalize: bool = False, derivative: bool = False, max_gain_db: float = 30.,
-                 freq_mask: Optional[float] = None, freq_mask_max_size: int = 80):
+                 freq_mask: Optional[float] = None, freq_mask_max_size: int = 80, resample_to: Optional[int] = None):
         self.normalize, self.derivative, self.max_gain_db = bool(normalize), bool(derivative), check_max_gain_db(max_gain_db)
         self.workspace = None
         if freq_mask is not None and not 0. <= freq_mask <= 1.:
@@ -224,6 +279,10 @@ class GpuBatchFeed:
             self.pitch = PitchTable(rand_pitch, p_pitch, max_factor)
             self.taps = torch.from_numpy(self.pitch.taps).to(pcm.device)
             self._means()
+        self.resample_to = self.res_taps = self.res_width = None       # None: no Resample (also when the rates are equal)
+        if resample_to is not None and resample_to != sr:
+            table, self.res_width = check_resample(sr, resample_to)
+            self.resample_to, self.res_taps = int(resample_to), table.contiguous().to(pcm.device)
 
     def _means(self) -> np.ndarray:
         """Mean of every (item, channel) row of int16 / 32767 (resample_poly's padtype='mean'), float64, computed on the device
@@ -252,9 +311,11 @@ class GpuBatchFeed:
         before."""
         if self.freq_mask is None and bands is not None:
             raise RuntimeError("GpuBatchFeed: bands given to a feed built without freq_mask")
-        if self.freq_mask is not None and (n_signal < 2 * MASK_BINS or n_signal % MASK_BINS):
-            raise RuntimeError(f"GpuBatchFeed: freq_mask needs n_signal to be a multiple of {MASK_BINS} of at least {2 * MASK_BINS}, "
-                               f"not {n_signal} (scipy.signal.stft would pad the item or shorten its window)")
+        n_out = n_signal if self.resample_to is None else sinc_resampled_length(n_signal, self.sr, self.resample_to)
+        if self.freq_mask is not None and (n_out < 2 * MASK_BINS or n_out % MASK_BINS):
+            what = "n_signal" if self.resample_to is None else f"the {n_out} samples Resample makes of n_signal = {n_signal}"
+            raise RuntimeError(f"GpuBatchFeed: freq_mask needs {what} to be a multiple of {MASK_BINS} of at least {2 * MASK_BINS}, "
+                               f"not {n_out} (scipy.signal.stft would pad the item or shorten its window)")
         drawn = draws is None
         if drawn:
             draws = self.draw(batch, n_signal)
@@ -271,7 +332,7 @@ class GpuBatchFeed:
         if noise is None:
             noise = torch.rand(rows, n_signal, device=dev, generator=self.gen)
         noise = noise.to(dev, torch.float32).contiguous()
-        out = torch.empty(batch, n_ch, n_signal, device=dev, dtype=torch.float32)
+        out = torch.empty(batch, n_ch, n_out, device=dev, dtype=torch.float32)
         dst = out                                   # where the chain writes: the batch itself unless a mask launch follows
         if bands is not None:
             if self.mask_input is None or self.mask_input.numel() < out.numel():     # regrown only when rows x n_signal grows
@@ -280,7 +341,7 @@ class GpuBatchFeed:
         pitched = ratios is not None and any(r is not None for r in ratios)
         muted = mute is not None and any(mute)
         post = self.normalize or self.derivative
-        if not (pitched or muted or post):
+        if not (pitched or muted or post or self.resample_to is not None):
             off = np.empty(rows, dtype=np.int64)
             coef = np.full((rows, 5), np.nan, dtype=np.float64)
             for b in range(batch):
@@ -316,6 +377,19 @@ class GpuBatchFeed:
                     row["tap_offset"] = self._tap_offset(ratio)
         table_d = torch.from_numpy(table.view(np.uint8)).to(dev)
         n_taps = 0 if self.taps is None else self.taps.numel()
+        if self.resample_to is not None:
+            need = L.lib.rh_feed_resample_workspace_bytes(rows, n_signal, self.sr, self.resample_to)
+            if need < 0:
+                raise RuntimeError(f"GpuBatchFeed: Resample {self.sr} -> {self.resample_to} of {n_signal} samples leaves int32")
+            if self.workspace is None or self.workspace.numel() * 8 < need:
+                self.workspace = torch.empty(need // 8, device=dev, dtype=torch.float64)
+            L.check(L.lib.rh_feed_batch_resample_i16_f32(L.ptr(self.pcm), self.pcm.numel(), table.ctypes.data, L.ptr(table_d),
+                                                         L.ptr(self.taps), n_taps, L.ptr(noise), rows, n_signal, self.bit_depth,
+                                                         n_ch, int(self.normalize), self.max_gain_db, int(self.derivative),
+                                                         self.sr, self.resample_to, L.ptr(self.res_taps), self.res_taps.numel(),
+                                                         self.res_width, L.ptr(self.workspace), self.workspace.numel() * 8,
+                                                         L.ptr(dst), L.stream()), "feed_batch_resample")
+            return self._mask(dst, out, bands)
         if post:
             need = L.lib.rh_feed_post_workspace_bytes(rows, n_signal)
             if self.workspace is None or self.workspace.numel() * 8 < need:            # regrown only when rows x n_signal grows

@@ -1,7 +1,9 @@
 """Throughput of the GPU data feed (rave_amd/data.py): batches of 32 x 65536 from 64 resident items.
 ``--rand-pitch lo,hi`` adds a leg with RandomPitch on (about half the items resampled), ``--post`` a leg with ``normalize``
 and ``derivative`` on (rh_feed_batch_post_i16_f32: the chain kernel plus the gain / difference kernel), ``--freq_mask P`` two
-legs with FrequencyMasking on (rh_feed_freq_mask_f32 behind the chain: every item masked, and a share P of them), ``--step`` the
+legs with FrequencyMasking on (rh_feed_freq_mask_f32 behind the chain: every item masked, and a share P of them),
+``--resample ORIG,NEW`` a leg with Resample(ORIG, NEW) behind Dequantize (rh_feed_batch_resample_i16_f32: the chain kernel plus the
+resampling kernel; with ``--post`` a second one with ``normalize`` and ``derivative`` behind it, three launches), ``--step`` the
 replayed v2 training step (bench.py's default workload) the feed has to hide under on a side stream -- all timed in the same
 process, with HIP events, in alternating windows.  The "feed" leg is the chain launch alone."""
 import argparse
@@ -16,6 +18,8 @@ ap.add_argument("--p-pitch", type=float, default=.5, help="share of the items th
 ap.add_argument("--post", action="store_true", help="also time the feed with normalize=True, derivative=True")
 ap.add_argument("--freq_mask", type=float, default=None, metavar="P",
                 help="also time the feed with FrequencyMasking: all items masked, and with probability P")
+ap.add_argument("--resample", default=None, metavar="ORIG,NEW",
+                help="also time the feed of a dataset stored at ORIG Hz resampled to NEW Hz (with --post: also with both steps)")
 ap.add_argument("--step", action="store_true", help="also time the replayed v2 training step at batch 32 x 65536")
 ap.add_argument("--reps", type=int, default=3, help="timed windows per leg, alternating between the legs")
 args = ap.parse_args()
@@ -31,6 +35,12 @@ if args.post:
 if args.freq_mask is not None:
     legs.append(("feed + freq_mask, all rows masked", D.GpuBatchFeed(pcm, seed=0, freq_mask=1.)))
     legs.append((f"feed + freq_mask (p = {args.freq_mask:g})", D.GpuBatchFeed(pcm, seed=0, freq_mask=args.freq_mask)))
+if args.resample:
+    orig, new = map(int, args.resample.split(","))
+    legs.append((f"feed + resample {orig} -> {new}", D.GpuBatchFeed(pcm, sr=orig, seed=0, resample_to=new)))
+    if args.post:
+        legs.append((f"feed + resample {orig} -> {new}, normalize + derivative",
+                     D.GpuBatchFeed(pcm, sr=orig, seed=0, resample_to=new, normalize=True, derivative=True)))
 
 
 class Step:
