@@ -267,11 +267,21 @@ int rh_conv1d_bwd_weight_wn_f32(const rh_conv1d_desc* d, const float* dy, const 
 /* Diagnostics: how many times this process took the one-launch form above (tests assert that it really runs). */
 int64_t rh_conv1d_bwd_weight_wn_fused_launches(void);
 
-/* ---- PQMF (rave/pqmf.py CachedPQMF, 16 bands) ------------------------------------------- */
+/* ---- PQMF (rave/pqmf.py CachedPQMF; M = n_band in {2, 4, 8, 16, 32}) ----------------------- */
+
+/* 1 iff the four transforms below take this band count and this analysis kernel length (the last dimension of
+ * forward_conv.weight): n_band in {2, 4, 8, 16, 32} and 1 <= kernel <= 40 * n_band (the launcher stages at most 40
+ * polyphase taps; the designed banks have kernel = 32 * n_band + 1, i.e. 33 taps).  Every other band count makes the
+ * entry points return RH_ERR_UNSUPPORTED.  16 runs on the MFMA kernels of pqmf.hip (and, from the Python layer, on the
+ * folded fast form below); the others on the vector-ALU kernels of pqmf_bands.hip. */
+int rh_pqmf_supported(int32_t n_band, int32_t kernel);
+/* Frames one workgroup of the direct-form kernels produces for this band count (0: no kernel); tests place their lengths
+ * around it. */
+int rh_pqmf_tile_frames(int32_t n_band);
 
 /* CachedPQMF.forward (rave/pqmf.py:279-283): strided Conv1d(1,M,K,stride=M,pad=(pad_left,*))
  * followed by reverse_half (:13-17).  x (rows, T) -> y (rows, M, n_frames) with
- * n_frames = (T + pad_left + pad_right - K)/M + 1.  w: forward_conv.weight (M,1,K). M must be 16. */
+ * n_frames = (T + pad_left + pad_right - K)/M + 1.  w: forward_conv.weight (M,1,K). */
 int rh_pqmf_analysis_fwd_f32(const float* x, const float* w, int32_t rows, int32_t t_len,
                              int32_t n_band, int32_t kernel, int32_t pad_left, int32_t n_frames,
                              float* y, rh_stream_t stream);

@@ -1,4 +1,5 @@
-// PQMF analysis / synthesis (rave/pqmf.py CachedPQMF, 16 bands) and their input gradients.
+// PQMF analysis / synthesis (rave/pqmf.py CachedPQMF, 16 bands) and their input gradients.  The entry points at the end
+// of this file send the other band counts (2, 4, 8, 32) to pqmf_bands.hip.
 //
 // All four transforms are the same GEMM in polyphase form,  M = 16, K = A*16, N = frames,
 // computed with v_mfma_f32_16x16x4_f32 (exact f32, k-ordered fmaf chain):
@@ -17,6 +18,7 @@
 // waveform frames / band rows into LDS (bank-conflict-free pitches), filter taps in LDS,
 // MFMA accumulators in registers, 16-byte coalesced stores.  HBM traffic = 8 B/sample.
 #include "common.hpp"
+#include "pqmf_bands.hpp"
 
 namespace {
 
@@ -197,16 +199,27 @@ int launch(const PqmfP& p, bool w2b, hipStream_t stream) {
 int check_common(const void* a, const void* b, const void* c, int rows, int n_band) {
     RH_REQUIRE(rows >= 0, RH_ERR_INVALID, "pqmf: rows < 0");
     RH_REQUIRE(rows == 0 || (a && b && c), RH_ERR_INVALID, "pqmf: null pointer");
-    RH_REQUIRE(n_band == kBands, RH_ERR_UNSUPPORTED, "pqmf: only n_band == 16 is implemented (got %d)", n_band);
+    RH_REQUIRE(n_band == kBands || rh_pqmf_bands_has(n_band), RH_ERR_UNSUPPORTED,
+               "pqmf: n_band must be one of 2, 4, 8, 16, 32 (got %d)", n_band);
     return RH_OK;
 }
 
 }  // namespace
 
+extern "C" int rh_pqmf_supported(int32_t n_band, int32_t kernel) {
+    if (n_band != kBands && !rh_pqmf_bands_has(n_band)) return 0;
+    return kernel > 0 && rh_cdiv(kernel, n_band) <= kMaxA;
+}
+
+extern "C" int rh_pqmf_tile_frames(int32_t n_band) {
+    return n_band == kBands ? kFramesPerBlock : rh_pqmf_bands_tile_frames(n_band);
+}
+
 extern "C" int rh_pqmf_analysis_fwd_f32(const float* x, const float* w, int32_t rows, int32_t t_len,
                                         int32_t n_band, int32_t kernel, int32_t pad_left,
                                         int32_t n_frames, float* y, rh_stream_t stream) {
     if (int e = check_common(x, w, y, rows, n_band)) return e;
+    if (n_band != kBands) return rh_pqmf_bands_analysis_fwd(x, w, rows, t_len, n_band, kernel, pad_left, n_frames, y, (hipStream_t)stream);
     PqmfP p{};
     p.in = x; p.w = w; p.out = y; p.rows = rows; p.in_len = t_len; p.out_len = n_frames;
     p.n_tiles = rh_cdiv(n_frames, kFramesPerBlock);
@@ -220,6 +233,7 @@ extern "C" int rh_pqmf_analysis_bwd_f32(const float* dy, const float* w, int32_t
                                         int32_t n_band, int32_t kernel, int32_t pad_left,
                                         int32_t n_frames, float* dx, rh_stream_t stream) {
     if (int e = check_common(dy, w, dx, rows, n_band)) return e;
+    if (n_band != kBands) return rh_pqmf_bands_analysis_bwd(dy, w, rows, t_len, n_band, kernel, pad_left, n_frames, dx, (hipStream_t)stream);
     PqmfP p{};
     p.in = dy; p.w = w; p.out = dx; p.rows = rows; p.in_len = n_frames; p.out_len = t_len;
     p.n_tiles = rh_cdiv(rh_cdiv(t_len, 16), kFramesPerBlock);
@@ -237,6 +251,7 @@ extern "C" int rh_pqmf_synthesis_fwd_f32(const float* y, const float* w, int32_t
                                          int32_t pad_left, int32_t n_out, float* x,
                                          rh_stream_t stream) {
     if (int e = check_common(y, w, x, rows, n_band)) return e;
+    if (n_band != kBands) return rh_pqmf_bands_synthesis_fwd(y, w, rows, n_frames, n_band, kernel, pad_left, n_out, x, (hipStream_t)stream);
     PqmfP p{};
     p.in = y; p.w = w; p.out = x; p.rows = rows; p.in_len = n_frames; p.out_len = n_out * 16;
     p.n_tiles = rh_cdiv(n_out, kFramesPerBlock);
@@ -251,6 +266,7 @@ extern "C" int rh_pqmf_synthesis_bwd_f32(const float* dx, const float* w, int32_
                                          int32_t pad_left, int32_t n_out, float* dy,
                                          rh_stream_t stream) {
     if (int e = check_common(dx, w, dy, rows, n_band)) return e;
+    if (n_band != kBands) return rh_pqmf_bands_synthesis_bwd(dx, w, rows, n_frames, n_band, kernel, pad_left, n_out, dy, (hipStream_t)stream);
     PqmfP p{};
     p.in = dx; p.w = w; p.out = dy; p.rows = rows; p.in_len = n_out * 16; p.out_len = n_frames;
     p.n_tiles = rh_cdiv(n_frames, kFramesPerBlock);

@@ -1,8 +1,10 @@
 """Drop-in for ``rave.pqmf.CachedPQMF`` (rave/pqmf.py:179-294) on the HIP PQMF kernels.
 
 Same constructor ``(attenuation, n_band, polyphase=True, n_channels=1)`` and the same
-``state_dict``: buffers ``hk (16,512)``, ``h (377,)``, parameters ``forward_conv.weight (16,1,513)``
-and ``inverse_conv.weight (16,16,33)``.  The prototype filter design is init-time host work (scipy)
+``state_dict``: buffers ``hk (M,32M)``, ``h``, parameters ``forward_conv.weight (M,1,32M+1)`` and ``inverse_conv.weight (M,M,33)``
+-- for the shipped M = 16: ``hk (16,512)``, ``h (377,)``, ``(16,1,513)`` and ``(16,16,33)``.  Band counts: 1 (pass-through), 2, 4, 8,
+16 and 32 (``N_BAND`` of configs/v1.gin rebound); 16 also has the folded fast form, the others run the direct-form kernels
+of rave_amd/csrc/pqmf_bands.hip.  The prototype filter design is init-time host work (scipy)
 and follows rave/pqmf.py:55-89 line by line with the current scipy spelling (``firwin(fs=2*pi)``
 == the pinned scipy 1.10 ``firwin(nyq=pi)``).
 
@@ -20,6 +22,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import _lib as L
 from . import cc, ops
 
 
@@ -108,7 +111,7 @@ class _FoldMixin:
             return cache[1]        # a hipGraph is being recorded: no host round trip (refresh_host_caches ran before)
         if cache is None or cache[0] != key:
             # the stored conv weight is hk plus the make_odd zero tap: compare the bank it actually holds
-            bank = w_fwd.detach().reshape(w_fwd.shape[0], -1)[:, :512]
+            bank = w_fwd.detach().reshape(w_fwd.shape[0], -1)[:, :self.hk.shape[-1]]
             ft = fold_tables(self.h, bank)
             cache = (key, None if ft is None else (ft[0].to(w_fwd.device), ft[1]))
             self._fold_cache = cache
@@ -129,11 +132,24 @@ def make_odd(x):
     return x
 
 
+def require_bands(n_band, kernel=None) -> None:
+    """NotImplementedError unless the HIP kernels take this band count (``rh_pqmf_supported``; 1 is the pass-through that
+    launches nothing) and, once the bank is designed, the analysis kernel length ``kernel`` it led to."""
+    if n_band == 1:
+        return
+    if not L.lib.rh_pqmf_supported(int(n_band), 1 if kernel is None else int(kernel)):
+        raise NotImplementedError(f"rave_amd.pqmf: the HIP kernels implement n_band in {{1, 2, 4, 8, 16, 32}}, each with an "
+                                  f"analysis kernel of at most 40 * n_band taps (got n_band = {n_band}"
+                                  + ("" if kernel is None else f", kernel = {kernel}") + ")")
+
+
 class CachedPQMF(_FoldMixin, nn.Module):
     def __init__(self, attenuation, n_band, polyphase=True, n_channels=1):
         super().__init__()
-        if n_band != 16 and n_band != 1:
-            raise NotImplementedError("rave_amd.pqmf: the HIP kernels implement the 16-band bank of the shipped configs")
+        if polyphase:                               # rave/pqmf.py:203-206, reached through CachedPQMF's super().__init__
+            power = math.log2(n_band)
+            assert power == math.floor(power), "when using the polyphase algorithm, n_band must be a power of 2"
+        require_bands(n_band)                       # before the filter design, which takes seconds
         h = torch.from_numpy(get_prototype(attenuation, n_band)).float()
         hk = center_pad_next_pow_2(get_qmf_bank(h, n_band))
         self.register_buffer("hk", hk)
@@ -143,6 +159,7 @@ class CachedPQMF(_FoldMixin, nn.Module):
         self.n_channels = n_channels
 
         hkf = make_odd(self.hk).unsqueeze(1)
+        require_bands(n_band, hkf.shape[-1])
         hki = self.hk.flip(-1)
         m = self.hk.shape[0]
         hki = hki.reshape(m, -1, m).permute(2, 0, 1)           # "c (t m) -> m c t"
@@ -161,13 +178,13 @@ class CachedPQMF(_FoldMixin, nn.Module):
         pass
 
     def forward(self, x):
-        """(B*C, 1, T) -> (B*C, 16, T/16), reverse_half fused (rave/pqmf.py:279-283)."""
+        """(B*C, 1, T) -> (B*C, M, T/M), reverse_half fused (rave/pqmf.py:279-283)."""
         if self.n_band == 1:
             return x
         return ops.pqmf_analysis(x, self.forward_conv.weight, self.forward_conv._pad, self._fold(self.forward_conv.weight))
 
     def inverse(self, x):
-        """(B*C, 16, N) -> (B*C, 1, 16 N); sign flip, x16, band reversal, interleave fused
+        """(B*C, M, N) -> (B*C, 1, M N); sign flip, xM, band reversal, interleave fused
         (rave/pqmf.py:285-294)."""
         if self.n_band == 1:
             return x
@@ -181,7 +198,7 @@ class CachedPQMF(_FoldMixin, nn.Module):
     def refresh_host_caches(self) -> None:
         """Re-validate the host-side decisions that depend on parameter VALUES (is the stored bank the closed-form
         one?) -- called before a hipGraph capture, during which no device-to-host copy is possible."""
-        if self.n_band == 16 and self._fold(self.forward_conv.weight) is not None:
+        if self._fold(self.forward_conv.weight) is not None:       # None for every band count but 16
             self._inverse_matches()
 
     def _inverse_matches(self) -> bool:
@@ -191,8 +208,8 @@ class CachedPQMF(_FoldMixin, nn.Module):
         if c is not None and w.is_cuda and torch.cuda.is_current_stream_capturing():
             return c[1]
         if c is None or c[0] != key:
-            hk = self.forward_conv.weight.detach().reshape(16, -1)[:, :512]
-            m = hk.shape[0]
+            m = self.forward_conv.weight.shape[0]
+            hk = self.forward_conv.weight.detach().reshape(m, -1)[:, :self.hk.shape[-1]]
             want = make_odd(hk.flip(-1).reshape(m, -1, m).permute(2, 0, 1))
             ok = bool(torch.equal(want.to(w.device), w.detach()))
             c = self._inv_ok = (key, ok)
@@ -203,19 +220,22 @@ class PQMF(_FoldMixin, nn.Module):
     """rave/pqmf.py:179-242, the non-cached filterbank (``polyphase_forward/inverse`` :92-134 or
     ``classic_forward/inverse`` :137-176; not bound by any shipped .gin, kept as the cross-check the reference
     itself uses).  state_dict: buffers ``hk``, ``h`` only.  Both analysis variants equal CachedPQMF.forward
-    (same 512 taps, pad 256); both synthesis variants equal CachedPQMF.inverse advanced by one frame of 16 samples
-    (the polyphase form pads 17 + 17 and crops two frames, :129-133), which on the HIP kernel is the pad pair
-    (15, 17) instead of (16, 16).  The kernel operands are non-persistent buffers derived from ``hk``."""
+    (same 32 M taps, pad 16 M); both synthesis variants equal CachedPQMF.inverse advanced by one frame of M samples.
+    With L = 32 M / M = 32 polyphase taps for every M, the polyphase form pads L/2 + 1 on both sides, drops the last frame
+    and crops 2 M samples = two frames (:128-133): frames 2 .. N+1 of a convolution padded (L/2 + 1, .), which are
+    frames 0 .. N-1 of one padded (L/2 - 1, L/2 + 1) -- on the HIP kernel the pad pair (15, 17) instead of (16, 16), for
+    every band count.  The classic form (:168-175: zero-stuffed input, pad 16 M, first sample dropped) is the same
+    signal.  The kernel operands are non-persistent buffers derived from ``hk``."""
 
     def __init__(self, attenuation, n_band, polyphase=True, n_channels=1):
         super().__init__()
-        if n_band != 16 and n_band != 1:
-            raise NotImplementedError("rave_amd.pqmf: the HIP kernels implement the 16-band bank of the shipped configs")
         if polyphase:
             power = math.log2(n_band)
             assert power == math.floor(power), "when using the polyphase algorithm, n_band must be a power of 2"
+        require_bands(n_band)
         h = torch.from_numpy(get_prototype(attenuation, n_band)).float()
         hk = center_pad_next_pow_2(get_qmf_bank(h, n_band))
+        require_bands(n_band, hk.shape[-1] + 1)
         self.register_buffer("hk", hk)
         self.register_buffer("h", h)
         self.n_band = n_band
@@ -242,5 +262,5 @@ class PQMF(_FoldMixin, nn.Module):
             return torch.stack([self.inverse(xi) for xi in x])
         if self.n_band == 1:
             return x
-        taps = self._w_inv.shape[-1] - 1          # 32 polyphase taps (+1 zero from make_odd)
+        taps = self._w_inv.shape[-1] - 1          # L = 32 polyphase taps for every band count (+1 zero from make_odd)
         return ops.pqmf_synthesis(x, self._w_inv, (taps // 2 - 1, taps // 2 + 1), self._fold(self._w_fwd))
