@@ -635,6 +635,34 @@ int rh_mel_fwd_f32(const float* x, const float* window, const float* twiddle, co
                    int64_t rows, int32_t t_len, int32_t n_fft, int32_t hop, int32_t n_mels, int32_t n_frames, float scale,
                    int32_t log1p, float* y, rh_stream_t stream);
 
+/* The complex spectrogram in front of the spectral discriminators, with its gradient:
+ * torchaudio.transforms.Spectrogram(n_fft, hop_length, power=None, normalized, center) followed by
+ * cat([s.real, s.imag], 1) (rave/discriminator.py:12-20,147-152, center = 0; rave/descript_discriminator.py:153-160,
+ * center = 1 with reflect padding), one launch per direction.  x (rows, t_len) f32, rows = batch * channels; window (n_fft,
+ * read from the buffer passed in); twiddle as for rh_stft_loss_fwd_f32 (e^{-2 pi i k / n_fft}, k < n_fft, 8-byte aligned).
+ *   out (batch, 2 * channels, n_fft / 2 + 1, frames):  out[b][p * channels + c][k][f] = scale * (p ? Im : Re)
+ *       sum_n window[n] xpad[b * channels + c][f * hop + n] e^{-2 pi i k n / n_fft}
+ * -- the reference's cat([real, imag], 1) itself; with channels = 1 it reads (rows, 2, bins, frames), plane 0 real, plane 1
+ * imaginary.  xpad = x (center = 0, frames = (t_len - n_fft) / hop + 1) or x reflect-padded by n_fft / 2 on either side,
+ * indexed in the kernel (center = 1, frames = t_len / hop + 1).  scale = 1 / sqrt(sum(window^2)) for `normalized=True`, else 1:
+ * the caller computes it.  n_fft = 4096 runs as a 2048-point complex transform.
+ * rh_spectrogram_bwd_f32 (replaces autograd through torch.stft at the same sites): dx (rows, t_len) = the exact adjoint
+ * applied to dout (laid out as out): the transpose of the real DFT (no Hermitian doubling), the window, overlap-add, the
+ * reflected edges folded back.  A workgroup owns a span of dx and transforms every frame that covers it: no workspace, no
+ * atomics, one writer and one fixed order of additions per sample -- bit-identical from run to run.
+ * Sizes (rh_spectrogram_supported answers 1 / 0; a host function): n_fft a power of two in 128 .. 4096, 1 <= hop <= n_fft
+ * (win_length == n_fft), t_len >= n_fft (center = 0) or t_len > n_fft / 2 (center = 1), t_len <= 2^30, 0 < rows < 65536 -- anything else is
+ * RH_ERR_UNSUPPORTED; null pointers, rows no multiple of channels, a misaligned twiddle table and a scale that is not
+ * positive and finite are RH_ERR_INVALID; nothing is enqueued in any of these cases.  x, out, dout and dx need only be
+ * 4-byte aligned (16-byte accesses are used where the pointer and the frame count allow them). */
+int rh_spectrogram_supported(int32_t n_fft, int32_t hop, int32_t t_len, int64_t rows, int32_t center);
+int rh_spectrogram_fwd_f32(const float* x, const float* window, const float* twiddle, int64_t rows, int32_t channels,
+                           int32_t t_len, int32_t n_fft, int32_t hop, int32_t center, float scale, float* out,
+                           rh_stream_t stream);
+int rh_spectrogram_bwd_f32(const float* dout, const float* window, const float* twiddle, int64_t rows, int32_t channels,
+                           int32_t t_len, int32_t n_fft, int32_t hop, int32_t center, float scale, float* dx,
+                           rh_stream_t stream);
+
 /* Measurement hook (bench.py's roofline leg; not part of the reference interface): arm a pair of HIP events (hipEvent_t,
  * created by the caller with timing enabled) for the calling thread's NEXT main kernel launch -- the convolution /
  * weight-gradient kernel of rh_conv1d_fwd_f32 / _bwd_data_f32 / _bwd_weight_f32 / rh_residual_unit_fwd_f32, not its split-K

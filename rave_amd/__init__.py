@@ -15,4 +15,7 @@ def __getattr__(name):
     if name == "MelSpectrogram":
         from .mel import MelSpectrogram
         return MelSpectrogram
+    if name == "Spectrogram":           # torchaudio.transforms.Spectrogram's stand-in (rave_amd/spectrogram.py)
+        from .spectrogram import Spectrogram
+        return Spectrogram
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

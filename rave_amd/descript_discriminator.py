@@ -17,6 +17,7 @@ import torch.nn.functional as F
 from . import cc, ops
 from .blocks import weight_norm
 from .discriminator import _period_major, run_conv2d_layer
+from .spectrogram import Spectrogram
 
 # frequency bands of the multi-resolution nets as fractions of the spectrum (descript_discriminator.py:115)
 BANDS = [(0.0, 0.1), (0.1, 0.25), (0.25, 0.5), (0.5, 0.75), (0.75, 1.0)]
@@ -81,14 +82,14 @@ class MPD(nn.Module):
         return fmap
 
 
-class _Stft(nn.Module):
+class _Stft(Spectrogram):
     """torchaudio Spectrogram(n_fft=w, hop=w/4, center=True, power=None) -> (B, C, frames, bins) complex:
-    HIP framing kernel (centre + reflect pad + Hann) + rocFFT.  Owns the ``window`` buffer."""
+    HIP framing kernel (centre + reflect pad + Hann) + rocFFT.  Owns the ``window`` buffer.  ``planes`` (the base class,
+    rave_amd/spectrogram.py) is the one-kernel front end that ``hip_frontend=True`` selects."""
 
     def __init__(self, n_fft: int, hop: int) -> None:
-        super().__init__()
-        self.n_fft, self.hop = n_fft, hop
-        self.register_buffer("window", torch.hann_window(n_fft))
+        super().__init__(n_fft=n_fft, hop_length=hop, power=None, normalized=False, center=True)
+        self.hop = hop
 
     def forward(self, x):
         b, c, t = x.shape
@@ -102,9 +103,10 @@ class MRD(nn.Module):
     5-conv net per frequency band, band outputs concatenated along frequency into a (3,3) scoring conv."""
 
     def __init__(self, window_length: int, hop_factor: float = 0.25, sample_rate: int = 44100, bands: list = BANDS,
-                 n_channels: int = 1):
+                 n_channels: int = 1, hip_frontend: bool = False):
         super().__init__()
         self.window_length, self.hop_factor, self.sample_rate = window_length, hop_factor, sample_rate
+        self.hip_frontend = bool(hip_frontend)
         n_bins = window_length // 2 + 1
         self.bands = [(int(lo * n_bins), int(hi * n_bins)) for lo, hi in bands]
 
@@ -119,6 +121,11 @@ class MRD(nn.Module):
         self.stft = _Stft(window_length, int(hop_factor * window_length))
 
     def spectrogram(self, x):
+        if self.hip_frontend:
+            # rave_amd/csrc/spectrogram.hip writes (b, c, re/im, bins, frames): upstream's "(c p) t f" is a transposed view
+            s = self.stft.planes(x)
+            s = s.reshape(s.shape[0], -1, s.shape[-2], s.shape[-1]).transpose(-1, -2)
+            return [s[..., lo:hi] for lo, hi in self.bands]
         s = torch.view_as_real(self.stft(x))                      # (b, c, frames, bins, re/im)
         b, c, t, f, p = s.shape
         s = s.permute(0, 1, 4, 2, 3).reshape(b, c * p, t, f)      # upstream: "b c f t p -> b (c p) t f"
@@ -140,12 +147,12 @@ class DescriptDiscriminator(nn.Module):
     on the DC-free, peak-normalised waveform."""
 
     def __init__(self, rates: list = [], periods: list = [2, 3, 5, 7, 11], fft_sizes: list = [2048, 1024, 512],
-                 sample_rate: int = 44100, bands: list = BANDS, n_channels: int = 1):
+                 sample_rate: int = 44100, bands: list = BANDS, n_channels: int = 1, hip_frontend: bool = False):
         super().__init__()
         if rates:
             raise NotImplementedError("rave_amd DescriptDiscriminator: MSD (rates != []) is unreachable upstream too")
         nets = [MPD(p, n_channels=n_channels) for p in periods]
-        nets.extend(MRD(f, sample_rate=sample_rate, bands=bands, n_channels=n_channels) for f in fft_sizes)
+        nets.extend(MRD(f, sample_rate=sample_rate, bands=bands, n_channels=n_channels, hip_frontend=hip_frontend) for f in fft_sizes)
         self.discriminators = nn.ModuleList(nets)
 
     def preprocess(self, y):

@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import cc, ops
+from . import spectrogram as _spectrogram
 from .blocks import normalization
 from .ops import ACT_LEAKY, ACT_NONE
 
@@ -157,14 +158,13 @@ class CombineDiscriminators(nn.Module):
 
 
 # --------------------------------------------------------------------------- spectral discriminator
-class Spectrogram(nn.Module):
+class Spectrogram(_spectrogram.Spectrogram):
     """torchaudio.transforms.Spectrogram(power=None) as the reference configures it; owns the same
-    ``window`` buffer (state_dict key ``...window``).  Framing + FFT stay on torch.stft / rocFFT."""
+    ``window`` buffer (state_dict key ``...window``).  ``forward``: framing + FFT on torch.stft / rocFFT; ``real_imag`` (the
+    base class, rave_amd/spectrogram.py): the HIP kernel, which ``hip_frontend=True`` selects."""
 
     def __init__(self, n_fft: int, hop_length: int, normalized: bool, center: bool) -> None:
-        super().__init__()
-        self.n_fft, self.hop_length, self.normalized, self.center = n_fft, hop_length, normalized, center
-        self.register_buffer("window", torch.hann_window(n_fft))
+        super().__init__(n_fft=n_fft, hop_length=hop_length, power=None, normalized=normalized, center=center)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         shape = x.shape
@@ -174,6 +174,9 @@ class Spectrogram(nn.Module):
         if self.normalized:   # torchaudio "window" normalisation
             s = s / self.window.pow(2.).sum().sqrt()
         return s.reshape(shape[:-1] + s.shape[-2:])
+
+    def refresh_host_caches(self) -> None:
+        """Nothing here: the owning discriminator reads the norm when its ``hip_frontend`` is on; ``forward`` never uses it."""
 
 
 def spectrogram(n_fft: int) -> Spectrogram:
@@ -240,16 +243,27 @@ class EncodecConvNet(nn.Module):
 
 
 class MultiScaleSpectralDiscriminator(nn.Module):
-    """rave/discriminator.py:139-153."""
+    """rave/discriminator.py:139-153.  ``hip_frontend``: the (real, imag) planes come from rave_amd/csrc/spectrogram.hip
+    (forward and gradient) instead of torch.stft + cat; same modules, same state_dict keys."""
 
-    def __init__(self, scales: Sequence[int], convnet, n_channels: int = 1) -> None:
+    def __init__(self, scales: Sequence[int], convnet, n_channels: int = 1, hip_frontend: bool = False) -> None:
         super().__init__()
+        self.hip_frontend = bool(hip_frontend)
         self.specs = nn.ModuleList([spectrogram(n) for n in scales])
         self.nets = nn.ModuleList([convnet(n_channels=n_channels) for _ in scales])
+
+    def refresh_host_caches(self) -> None:
+        """Before GraphedTrainingStep records: the kernel's window norms are read on the host, outside the capture."""
+        if self.hip_frontend:
+            for spec in self.specs:
+                super(Spectrogram, spec).refresh_host_caches()
 
     def forward(self, x):
         features = []
         for spec, net in zip(self.specs, self.nets):
+            if self.hip_frontend:
+                features.append(net(spec.real_imag(x)))
+                continue
             spec_x = spec(x)
             spec_x = torch.cat([spec_x.real, spec_x.imag], 1)
             features.append(net(spec_x))

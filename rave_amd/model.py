@@ -821,7 +821,7 @@ def build_v2(n_channels: int = 1, capacity: int = 96, ratios=(4, 4, 4, 2), laten
              codebook_size: int = 1024, log_epsilon: float = 1e-7, num_skipped_features: int = 1,
              spectral_capacity: int = 32, gru_layers: int = 0, mel_input: bool = False, n_fft: int = 2048,
              hop_length: int = 256, n_mels: int = 128, encoder_ratios=(2, 2, 2), encoder_dilations=(1,),
-             latent_analysis: bool = False) -> RAVE:
+             latent_analysis: bool = False, hip_frontend: bool = False) -> RAVE:
     """configs/v1.gin + configs/v2.gin transcribed (cf. oracle/ref_models.py for the citations).
     ``snake`` / ``adain`` add the generator-side overlays of configs/v3.gin (snake.gin: every activation
     -> blocks.Snake; adain.gin: AdaptiveInstanceNormalization before every unit); ``causal`` =
@@ -833,7 +833,9 @@ def build_v2(n_channels: int = 1, capacity: int = 96, ratios=(4, 4, 4, 2), laten
     (``n_fft``, ``hop_length``, ``n_mels``, normalized) and EncoderV2(data_size = n_mels * n_channels as the reference's
     encoder computes it, ``encoder_ratios``, ``encoder_dilations``); the decoder keeps ``ratios`` / ``dilations``.
     ``latent_analysis`` registers the reference's ``latent_pca`` / ``latent_mean`` / ``fidelity`` buffers (rave/model.py:196-198),
-    which ``validation_epoch_end`` then fills; off by default, the state_dict keys are then unchanged."""
+    which ``validation_epoch_end`` then fills; off by default, the state_dict keys are then unchanged.
+    ``hip_frontend`` hands the complex spectrograms of the "spectral" and "descript" discriminators to
+    rave_amd/csrc/spectrogram.hip (the gin route: rave_amd/configs/mi355x_spectrogram*.gin); off by default."""
     ratios = list(ratios)
     spectrogram = None
     if mel_input:
@@ -893,9 +895,9 @@ def build_v2(n_channels: int = 1, capacity: int = 96, ratios=(4, 4, 4, 2), laten
     if discriminator_kind == "v2":
         disc = partial(discriminator.CombineDiscriminators, discriminators=[mpd, msd])
     elif discriminator_kind == "descript":
-        disc = descript_discriminator.DescriptDiscriminator
+        disc = partial(descript_discriminator.DescriptDiscriminator, hip_frontend=hip_frontend)
     elif discriminator_kind == "spectral":   # configs/spectral_discriminator.gin
-        mssd = partial(discriminator.MultiScaleSpectralDiscriminator, scales=[4096, 2048, 1024, 512, 256],
+        mssd = partial(discriminator.MultiScaleSpectralDiscriminator, scales=[4096, 2048, 1024, 512, 256], hip_frontend=hip_frontend,
                        convnet=partial(discriminator.EncodecConvNet, capacity=spectral_capacity))
         disc = partial(discriminator.CombineDiscriminators, discriminators=[msd, mssd])
     else:

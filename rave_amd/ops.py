@@ -1371,6 +1371,86 @@ def mel_spectrogram(x: Tensor, window: Tensor, fb: Tensor, bins: Tensor, hop: in
     return y
 
 
+# --------------------------------------------------------------------------- complex spectrogram (discriminator front ends)
+def spectrogram_supported(n_fft: int, hop: int, t: int, rows: int, center: bool) -> bool:
+    return L.lib.rh_spectrogram_supported(int(n_fft), int(hop), int(t), int(rows), int(bool(center))) == 1
+
+
+def spectrogram_scale(window: Tensor) -> float:
+    """1 / sqrt(sum(window^2)) of torchaudio's ``normalized=True``, computed on the host in float64 from the CURRENT buffer:
+    a host read, which a hipGraph capture cannot hold (rave_amd.Spectrogram caches it per buffer version)."""
+    if window.is_cuda and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("rave_amd spectrogram: the window's norm is read on the host; inside a hipGraph capture pass `scale`")
+    return float(window.detach().double().pow(2).sum().rsqrt())
+
+
+def spectrogram_compose(x: Tensor, window: Tensor, n_fft: int, hop: int, normalized: bool, center: bool,
+                        cat_channels: bool = False) -> Tensor:
+    """The torch composition (torch.stft on rocFFT / the CPU, the statements of rave_amd/discriminator.py:169-176): what CPU
+    tensors and unbuilt sizes take, and what tools/bench_spectrogram.py times against the kernels."""
+    shape = x.shape
+    window = window.to(x.dtype)
+    s = torch.stft(x.reshape(-1, shape[-1]), n_fft, hop_length=hop, win_length=n_fft, window=window, center=center,
+                   pad_mode="reflect", normalized=False, onesided=True, return_complex=True)
+    if normalized:
+        s = s / window.pow(2.).sum().sqrt()
+    s = s.reshape(shape[:-1] + s.shape[-2:])
+    if cat_channels:
+        return torch.cat([s.real, s.imag], 1)
+    return torch.stack([s.real, s.imag], -3)
+
+
+class _SpectrogramFn(torch.autograd.Function):
+    """rh_spectrogram_fwd_f32 / rh_spectrogram_bwd_f32.  x and dout are plain f32, no x6 operands: no range slots."""
+
+    @staticmethod
+    def forward(ctx, x, window, n_fft: int, hop: int, scale: float, center: bool, cat_channels: bool):
+        x = _chk(x, "x"); window = _chk(window, "window")
+        t = x.shape[-1]
+        rows = x.numel() // max(t, 1)
+        frames = t // hop + 1 if center else (t - n_fft) // hop + 1
+        channels = x.shape[1] if cat_channels else 1
+        lead = (x.shape[0],) if cat_channels else x.shape[:-1]
+        out = torch.empty(lead + (2 * channels, n_fft // 2 + 1, frames), device=x.device, dtype=torch.float32)
+        L.check(L.lib.rh_spectrogram_fwd_f32(L.ptr(x), L.ptr(window), L.ptr(_twiddle(n_fft, x.device)), rows, channels, t, n_fft,
+                                             hop, int(center), scale, L.ptr(out), L.stream()), "spectrogram_fwd")
+        ctx.save_for_backward(window)
+        ctx.geom = (tuple(x.shape), rows, n_fft, hop, scale, center, channels)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (window,) = ctx.saved_tensors
+        shape, rows, n_fft, hop, scale, center, channels = ctx.geom
+        dout = _chk(dout, "dout")
+        dx = torch.empty(shape, device=dout.device, dtype=torch.float32)
+        L.check(L.lib.rh_spectrogram_bwd_f32(L.ptr(dout), L.ptr(window), L.ptr(_twiddle(n_fft, dout.device)), rows, channels,
+                                             shape[-1], n_fft, hop, int(center), scale, L.ptr(dx), L.stream()), "spectrogram_bwd")
+        return dx, None, None, None, None, None, None
+
+
+def spectrogram(x: Tensor, window: Tensor, n_fft: int, hop: int, normalized: bool, center: bool,
+                cat_channels: bool = False, scale: Optional[float] = None) -> Tensor:
+    """torchaudio.transforms.Spectrogram(n_fft, hop_length=hop, power=None, normalized, center) of x (..., T) as (real, imag)
+    planes, differentiable in x: (..., 2, n_fft // 2 + 1, frames), or with ``cat_channels`` and x (B, C, T) the reference's
+    ``cat([s.real, s.imag], 1)`` (B, 2 C, bins, frames) (rave/discriminator.py:147-152), written in place by the kernel.
+    GPU f32 tensors of a built size (rh_spectrogram_supported) run rave_amd/csrc/spectrogram.hip; CPU tensors and every other
+    size take the torch composition.  ``scale``: spectrogram_scale(window) where the caller has it already."""
+    n_fft, hop, center = int(n_fft), int(hop), bool(center)
+    if cat_channels and x.dim() != 3:
+        raise RuntimeError("rave_amd spectrogram: cat_channels needs x (B, C, T)")
+    t = x.shape[-1]
+    rows = x.numel() // max(t, 1)
+    if not (x.is_cuda and x.dtype == torch.float32 and window.numel() == n_fft
+            and spectrogram_supported(n_fft, hop, t, rows, center)):
+        return spectrogram_compose(x, window, n_fft, hop, normalized, center, cat_channels)
+    if not normalized:
+        scale = 1.0
+    elif scale is None:
+        scale = spectrogram_scale(window)
+    return _SpectrogramFn.apply(x, window, n_fft, hop, scale, center, bool(cat_channels))
+
+
 # --------------------------------------------------------------------------- reparametrisation + KL
 class _ReparamFn(torch.autograd.Function):
     """VariationalEncoder.reparametrize (rave/blocks.py:727-745) on rh_reparam_{fwd,bwd}_f32: (zs, kl) from z = [mean | scale]
