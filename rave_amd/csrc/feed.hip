@@ -9,7 +9,8 @@
 // At > 1e8 samples/s per GPU the 8-worker scipy chain cannot keep up; here a (clip, channel) row is one workgroup:
 // 4096-sample chunks are staged in LDS, thread 0 advances the two-state recurrence, all threads add the noise and
 // store.  The recurrence is sequential by nature (0.5 ms for 65536 samples) but rows run in parallel and the
-// kernel is meant for a side stream, under the training step.
+// kernel is meant for a side stream, under the training step.  That is rh_feed_batch_i16_f32; the options below ride on a row table
+// and their three entry points are one runner (feed_run): rave_amd/data.py calls the widest, rh_feed_batch_resample_i16_f32.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -18,6 +19,30 @@
 namespace {
 
 constexpr int kChunk = 4096;
+
+// thread 0's part of a staged chunk: the all-pass in place, direct form II transposed, its two states carried to the next chunk
+__device__ __forceinline__ void feed_allpass(double* buf, int len, double b0, double b1, double b2, double a1, double a2,
+                                             double& z0, double& z1) {
+    for (int i = 0; i < len; ++i) {
+        const double x = buf[i];
+        const double y = b0 * x + z0;
+        z0 = b1 * x - a1 * y + z1;
+        z1 = b2 * x - a2 * y;
+        buf[i] = y;
+    }
+}
+
+// max of `v` over the 256 threads through `red` (256 doubles of LDS), stored by thread 0; max is exact, so any reduction
+// order gives the same bits
+__device__ __forceinline__ void feed_store_max(double* red, double v, double* dst) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + s]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *dst = red[0];
+}
 
 __global__ __launch_bounds__(256) void feed_kernel(const int16_t* __restrict__ pcm, const int64_t* __restrict__ src_offset,
                                                    const double* __restrict__ coef, const float* __restrict__ noise,
@@ -33,15 +58,7 @@ __global__ __launch_bounds__(256) void feed_kernel(const int16_t* __restrict__ p
         for (int i = threadIdx.x; i < len; i += 256)
             buf[i] = (double)((float)src[c0 + i] / 32767.0f);          // float32 division, as the reference
         __syncthreads();
-        if (filt && threadIdx.x == 0) {
-            for (int i = 0; i < len; ++i) {
-                const double x = buf[i];
-                const double y = b0 * x + z0;
-                z0 = b1 * x - a1 * y + z1;
-                z1 = b2 * x - a2 * y;
-                buf[i] = y;
-            }
-        }
+        if (filt && threadIdx.x == 0) feed_allpass(buf, len, b0, b1, b2, a1, a2, z0, z1);
         __syncthreads();
         for (int i = threadIdx.x; i < len; i += 256) {
             const long o = (long)r * n_signal + c0 + i;
@@ -141,15 +158,7 @@ __global__ __launch_bounds__(256) void feed_pitch_kernel(const int16_t* __restri
                 __syncthreads();
             }
         }
-        if (filt && threadIdx.x == 0) {
-            for (int i = 0; i < len; ++i) {
-                const double x = buf[i];
-                const double y = b0 * x + z0;
-                z0 = b1 * x - a1 * y + z1;
-                z1 = b2 * x - a2 * y;
-                buf[i] = y;
-            }
-        }
+        if (filt && threadIdx.x == 0) feed_allpass(buf, len, b0, b1, b2, a1, a2, z0, z1);
         __syncthreads();
         for (int i = threadIdx.x; i < len; i += 256) {
             const long o = (long)r * n_signal + c0 + i;
@@ -163,15 +172,7 @@ __global__ __launch_bounds__(256) void feed_pitch_kernel(const int16_t* __restri
         }
         __syncthreads();
     }
-    if constexpr (kPost) {                      // max is exact: any reduction order gives the same bits
-        buf[threadIdx.x] = peak;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if ((int)threadIdx.x < s) buf[threadIdx.x] = fmax(buf[threadIdx.x], buf[threadIdx.x + s]);
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) peaks[r] = buf[0];
-    }
+    if constexpr (kPost) feed_store_max(buf, peak, peaks + r);
 }
 
 // ---- normalize_signal and the derivator behind Dequantize (`rave train --normalize / --derivative`) ---------------------
@@ -295,15 +296,9 @@ __global__ __launch_bounds__(256) void feed_resample_kernel(const double* __rest
         }
         // no barrier: the next pass writes ybuf only behind its own first barrier, and span only after every thread is past the one above
     }
-    if constexpr (kPost) {                      // max is exact: any reduction order gives the same bits
+    if constexpr (kPost) {
         __shared__ double red[256];
-        red[threadIdx.x] = peak;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if ((int)threadIdx.x < s) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + s]);
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) peaks2[r] = red[0];
+        feed_store_max(red, peak, peaks2 + r);
     }
 }
 
@@ -348,6 +343,82 @@ int feed_check_rows(const char* what, int64_t pcm_samples, const rh_feed_pitch_r
     return RH_OK;
 }
 
+// The workspace of a call with a stage behind the chain kernel, as offsets in doubles: the chain's float64 rows first, one peak
+// per row at `peaks`, then -- n_res > 0: Resample runs -- the resampled rows at `ws2` and their peaks at `peaks2`.
+struct FeedLayout { int64_t peaks, ws2, peaks2, bytes; };
+FeedLayout feed_layout(int32_t n_rows, int32_t n_signal, int32_t n_res) {
+    const int64_t peaks = (int64_t)n_rows * n_signal, ws2 = peaks + n_rows, peaks2 = ws2 + (int64_t)n_rows * n_res;
+    return {peaks, ws2, peaks2, (peaks2 + (n_res > 0 ? n_rows : 0)) * (int64_t)sizeof(double)};
+}
+
+// Everything a table-driven call can carry, in the argument order of rh_feed_batch_resample_i16_f32 (include/rave_hip.h); an
+// entry point without the later arguments fills them with values that switch their stage off.
+struct FeedChain {
+    const int16_t* pcm; int64_t pcm_samples;
+    const rh_feed_pitch_row *rows, *rows_dev;
+    const double* taps; int32_t n_taps;
+    const float* noise;
+    int32_t n_rows, n_signal, bit_depth, n_channels, normalize; double max_gain_db; int32_t derivative;
+    int32_t orig_freq, new_freq; const float* res_taps; int64_t n_res_taps; int32_t width;
+    void* workspace; int64_t workspace_bytes;
+    float* out; rh_stream_t stream;
+};
+
+// The three table-driven entry points: which stages run, the checks, the workspace, the launches.  Messages carry the name of
+// the entry point the call reduces to (equal rates: feed_batch_post; both steps off as well: feed_batch_pitch), except that
+// the first checks, which feed_batch_post makes before it looks at its flags and feed_batch_pitch passes, carry `entry`.
+int feed_run(const char* entry, const FeedChain& c) {
+    RH_REQUIRE(c.orig_freq >= 1 && c.new_freq >= 1, RH_ERR_INVALID, "feed_batch_resample: rates %d -> %d", c.orig_freq, c.new_freq);
+    const bool resample = c.orig_freq != c.new_freq;        // equal rates: Resample returns its input
+    const bool post = c.normalize || c.derivative, staged = resample || post;      // staged: the chain kernel writes the workspace
+    const char* what = resample ? "feed_batch_resample" : post ? "feed_batch_post" : "feed_batch_pitch";
+    if (resample) entry = what;
+    RH_REQUIRE(c.n_rows >= 0 && c.n_signal > 0 && c.bit_depth > 0 && c.bit_depth < 32 && c.pcm_samples >= 0 && c.n_taps >= 0,
+               RH_ERR_INVALID, "%s: bad sizes", entry);
+    RH_REQUIRE(c.n_channels >= 1 && c.n_rows % c.n_channels == 0, RH_ERR_INVALID, "%s: %d rows are not whole items of %d channels",
+               entry, c.n_rows, c.n_channels);
+    RH_REQUIRE(std::isfinite(c.max_gain_db), RH_ERR_INVALID, "%s: max_gain_db is not finite", entry);
+    ResPlan p = {};                                         // n_res = 0: no resampled region in the workspace
+    if (resample) {
+        RH_REQUIRE(feed_resample_plan(c.orig_freq, c.new_freq, c.n_signal, &p), RH_ERR_INVALID,
+                   "feed_batch_resample: %d samples at %d -> %d leave int32", c.n_signal, c.orig_freq, c.new_freq);
+        RH_REQUIRE(c.width == p.width, RH_ERR_INVALID, "feed_batch_resample: width %d, but %d -> %d has ceil(6 o / (.99 min(o, n))) = %d",
+                   c.width, c.orig_freq, c.new_freq, p.width);
+        RH_REQUIRE(c.n_res_taps == (int64_t)p.n * p.K, RH_ERR_INVALID, "feed_batch_resample: table of %lld taps, %d x %d needed",
+                   (long long)c.n_res_taps, p.n, p.K);
+        RH_REQUIRE(p.K <= kResSpan, RH_ERR_INVALID, "feed_batch_resample: %d taps per filter exceed kResSpan = %d", p.K, kResSpan);
+        RH_REQUIRE(p.n <= kResOut, RH_ERR_INVALID, "feed_batch_resample: %d filters exceed kResOut = %d", p.n, kResOut);
+    }
+    if (c.n_rows == 0) return RH_OK;
+    RH_REQUIRE(c.pcm && c.rows && c.rows_dev && c.noise && (c.res_taps || !resample) && c.out, RH_ERR_INVALID, "%s: null pointer", what);
+    const FeedLayout l = feed_layout(c.n_rows, c.n_signal, p.n_res);
+    const int n_out = resample ? p.n_res : c.n_signal;      // samples per finished row
+    const int tiles = (n_out + kPostTile - 1) / kPostTile;
+    if (staged) {
+        RH_REQUIRE(c.workspace && c.workspace_bytes >= l.bytes, RH_ERR_INVALID, "%s: workspace of %lld bytes, %lld needed", what,
+                   (long long)c.workspace_bytes, (long long)l.bytes);
+        RH_REQUIRE((uintptr_t)c.workspace % 8 == 0, RH_ERR_INVALID, "%s: workspace is not 8-byte aligned", what);
+        RH_REQUIRE((int64_t)c.n_rows * tiles <= 0x7fffffffll, RH_ERR_INVALID, "%s: too many tiles for one launch", what);
+    }
+    if (const int rc = feed_check_rows(what, c.pcm_samples, c.rows, c.taps, c.n_taps, c.n_rows, c.n_signal)) return rc;
+    double *ws = nullptr, *peaks = nullptr, *ws2 = nullptr, *peaks2 = nullptr;      // null for the stages that do not run
+    if (staged) ws = (double*)c.workspace, peaks = ws + l.peaks;
+    if (resample && post) ws2 = ws + l.ws2, peaks2 = ws + l.peaks2;
+    hipLaunchKernelGGL(staged ? feed_pitch_kernel<true> : feed_pitch_kernel<false>, dim3(c.n_rows), dim3(256), 0, (hipStream_t)c.stream, c.pcm,
+                       c.rows_dev, c.taps, c.noise, c.n_signal, 1.0 / (double)(1ll << c.bit_depth), c.out, ws, peaks);
+    if (const int rc = rh_check_launch(what)) return rc;
+    if (resample) {
+        hipLaunchKernelGGL(post ? feed_resample_kernel<true> : feed_resample_kernel<false>, dim3(c.n_rows), dim3(256), 0, (hipStream_t)c.stream,
+                           (const double*)ws, c.rows_dev, c.res_taps, c.n_signal, p.n_res, p.o, p.n, p.K, p.width, c.out, ws2, peaks2);
+        if (const int rc = rh_check_launch("feed_batch_resample: resample")) return rc;
+    }
+    if (!post) return RH_OK;
+    hipLaunchKernelGGL(feed_post_kernel, dim3(c.n_rows * tiles), dim3(256), 0, (hipStream_t)c.stream,
+                       (const double*)(resample ? ws2 : ws), (const double*)(resample ? peaks2 : peaks), c.rows_dev, n_out, tiles,
+                       c.n_channels, c.normalize, c.max_gain_db, c.derivative, c.out);
+    return rh_check_launch(resample ? "feed_batch_resample: normalize / derivative" : "feed_batch_post: normalize / derivative");
+}
+
 }  // namespace
 
 extern "C" int rh_feed_batch_i16_f32(const int16_t* pcm, const int64_t* src_offset, const double* coef, const float* noise,
@@ -364,19 +435,13 @@ extern "C" int rh_feed_batch_pitch_i16_f32(const int16_t* pcm, int64_t pcm_sampl
                                            const rh_feed_pitch_row* rows_dev, const double* taps, int32_t n_taps,
                                            const float* noise, int32_t n_rows, int32_t n_signal, int32_t bit_depth, float* out,
                                            rh_stream_t stream) {
-    RH_REQUIRE(n_rows >= 0 && n_signal > 0 && bit_depth > 0 && bit_depth < 32 && pcm_samples >= 0 && n_taps >= 0, RH_ERR_INVALID,
-               "feed_batch_pitch: bad sizes");
-    if (n_rows == 0) return RH_OK;
-    RH_REQUIRE(pcm && rows && rows_dev && noise && out, RH_ERR_INVALID, "feed_batch_pitch: null pointer");
-    if (const int rc = feed_check_rows("feed_batch_pitch", pcm_samples, rows, taps, n_taps, n_rows, n_signal)) return rc;
-    hipLaunchKernelGGL(feed_pitch_kernel<false>, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, pcm, rows_dev, taps, noise,
-                       n_signal, 1.0 / (double)(1ll << bit_depth), out, (double*)nullptr, (double*)nullptr);
-    return rh_check_launch("feed_batch_pitch");
+    return feed_run("feed_batch_pitch", {pcm, pcm_samples, rows, rows_dev, taps, n_taps, noise, n_rows, n_signal, bit_depth,
+                                         /* one channel, no step, equal rates */ 1, 0, 0.0, 0, 1, 1, nullptr, 0, 0, nullptr, 0, out, stream});
 }
 
 extern "C" int64_t rh_feed_post_workspace_bytes(int32_t n_rows, int32_t n_signal) {
     if (n_rows < 0 || n_signal <= 0) return -1;
-    return ((int64_t)n_rows * n_signal + n_rows) * (int64_t)sizeof(double);      // the float64 rows, then one peak per row
+    return feed_layout(n_rows, n_signal, 0).bytes;
 }
 
 extern "C" int rh_feed_batch_post_i16_f32(const int16_t* pcm, int64_t pcm_samples, const rh_feed_pitch_row* rows,
@@ -384,40 +449,16 @@ extern "C" int rh_feed_batch_post_i16_f32(const int16_t* pcm, int64_t pcm_sample
                                           const float* noise, int32_t n_rows, int32_t n_signal, int32_t bit_depth,
                                           int32_t n_channels, int32_t normalize, double max_gain_db, int32_t derivative,
                                           void* workspace, int64_t workspace_bytes, float* out, rh_stream_t stream) {
-    RH_REQUIRE(n_rows >= 0 && n_signal > 0 && bit_depth > 0 && bit_depth < 32 && pcm_samples >= 0 && n_taps >= 0, RH_ERR_INVALID,
-               "feed_batch_post: bad sizes");
-    RH_REQUIRE(n_channels >= 1 && n_rows % n_channels == 0, RH_ERR_INVALID,
-               "feed_batch_post: %d rows are not whole items of %d channels", n_rows, n_channels);
-    RH_REQUIRE(std::isfinite(max_gain_db), RH_ERR_INVALID, "feed_batch_post: max_gain_db is not finite");
-    if (!normalize && !derivative)              // nothing behind Dequantize: the pitched feed itself, no workspace needed
-        return rh_feed_batch_pitch_i16_f32(pcm, pcm_samples, rows, rows_dev, taps, n_taps, noise, n_rows, n_signal, bit_depth, out,
-                                           stream);
-    if (n_rows == 0) return RH_OK;
-    RH_REQUIRE(pcm && rows && rows_dev && noise && out, RH_ERR_INVALID, "feed_batch_post: null pointer");
-    const int64_t need = rh_feed_post_workspace_bytes(n_rows, n_signal);
-    RH_REQUIRE(workspace && workspace_bytes >= need, RH_ERR_INVALID, "feed_batch_post: workspace of %lld bytes, %lld needed",
-               (long long)workspace_bytes, (long long)need);
-    RH_REQUIRE((uintptr_t)workspace % 8 == 0, RH_ERR_INVALID, "feed_batch_post: workspace is not 8-byte aligned");
-    const int tiles = (n_signal + kPostTile - 1) / kPostTile;
-    RH_REQUIRE((int64_t)n_rows * tiles <= 0x7fffffffll, RH_ERR_INVALID, "feed_batch_post: too many tiles for one launch");
-    if (const int rc = feed_check_rows("feed_batch_post", pcm_samples, rows, taps, n_taps, n_rows, n_signal)) return rc;
-    double* ws = (double*)workspace;
-    double* peaks = ws + (int64_t)n_rows * n_signal;
-    hipLaunchKernelGGL(feed_pitch_kernel<true>, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, pcm, rows_dev, taps, noise,
-                       n_signal, 1.0 / (double)(1ll << bit_depth), out, ws, peaks);
-    if (const int rc = rh_check_launch("feed_batch_post")) return rc;
-    hipLaunchKernelGGL(feed_post_kernel, dim3(n_rows * tiles), dim3(256), 0, (hipStream_t)stream, (const double*)ws,
-                       (const double*)peaks, rows_dev, n_signal, tiles, n_channels, normalize, max_gain_db, derivative, out);
-    return rh_check_launch("feed_batch_post: normalize / derivative");
+    return feed_run("feed_batch_post", {pcm, pcm_samples, rows, rows_dev, taps, n_taps, noise, n_rows, n_signal, bit_depth, n_channels,
+                                        normalize, max_gain_db, derivative, /* equal rates */ 1, 1, nullptr, 0, 0, workspace,
+                                        workspace_bytes, out, stream});
 }
 
 extern "C" int64_t rh_feed_resample_workspace_bytes(int32_t n_rows, int32_t n_signal, int32_t orig_freq, int32_t new_freq) {
     if (n_rows < 0 || n_signal <= 0 || orig_freq < 1 || new_freq < 1) return -1;
-    const int64_t chain = rh_feed_post_workspace_bytes(n_rows, n_signal);
-    if (orig_freq == new_freq) return chain;
-    ResPlan p;
-    if (!feed_resample_plan(orig_freq, new_freq, n_signal, &p)) return -1;
-    return chain + rh_feed_post_workspace_bytes(n_rows, p.n_res);                // the chain's rows and peaks, then the resampled ones
+    ResPlan p = {};
+    if (orig_freq != new_freq && !feed_resample_plan(orig_freq, new_freq, n_signal, &p)) return -1;
+    return feed_layout(n_rows, n_signal, p.n_res).bytes;
 }
 
 extern "C" int rh_feed_batch_resample_i16_f32(const int16_t* pcm, int64_t pcm_samples, const rh_feed_pitch_row* rows,
@@ -427,49 +468,7 @@ extern "C" int rh_feed_batch_resample_i16_f32(const int16_t* pcm, int64_t pcm_sa
                                               int32_t orig_freq, int32_t new_freq, const float* res_taps, int64_t n_res_taps,
                                               int32_t width, void* workspace, int64_t workspace_bytes, float* out,
                                               rh_stream_t stream) {
-    RH_REQUIRE(orig_freq >= 1 && new_freq >= 1, RH_ERR_INVALID, "feed_batch_resample: rates %d -> %d", orig_freq, new_freq);
-    if (orig_freq == new_freq)                  // Resample returns its input: the feed without it, same bits
-        return rh_feed_batch_post_i16_f32(pcm, pcm_samples, rows, rows_dev, taps, n_taps, noise, n_rows, n_signal, bit_depth,
-                                          n_channels, normalize, max_gain_db, derivative, workspace, workspace_bytes, out, stream);
-    RH_REQUIRE(n_rows >= 0 && n_signal > 0 && bit_depth > 0 && bit_depth < 32 && pcm_samples >= 0 && n_taps >= 0, RH_ERR_INVALID,
-               "feed_batch_resample: bad sizes");
-    RH_REQUIRE(n_channels >= 1 && n_rows % n_channels == 0, RH_ERR_INVALID,
-               "feed_batch_resample: %d rows are not whole items of %d channels", n_rows, n_channels);
-    RH_REQUIRE(std::isfinite(max_gain_db), RH_ERR_INVALID, "feed_batch_resample: max_gain_db is not finite");
-    ResPlan p;
-    RH_REQUIRE(feed_resample_plan(orig_freq, new_freq, n_signal, &p), RH_ERR_INVALID,
-               "feed_batch_resample: %d samples at %d -> %d leave int32", n_signal, orig_freq, new_freq);
-    RH_REQUIRE(width == p.width, RH_ERR_INVALID, "feed_batch_resample: width %d, but %d -> %d has ceil(6 o / (.99 min(o, n))) = %d",
-               width, orig_freq, new_freq, p.width);
-    RH_REQUIRE(n_res_taps == (int64_t)p.n * p.K, RH_ERR_INVALID, "feed_batch_resample: table of %lld taps, %d x %d needed",
-               (long long)n_res_taps, p.n, p.K);
-    RH_REQUIRE(p.K <= kResSpan, RH_ERR_INVALID, "feed_batch_resample: %d taps per filter exceed kResSpan = %d", p.K, kResSpan);
-    RH_REQUIRE(p.n <= kResOut, RH_ERR_INVALID, "feed_batch_resample: %d filters exceed kResOut = %d", p.n, kResOut);
-    if (n_rows == 0) return RH_OK;
-    RH_REQUIRE(pcm && rows && rows_dev && noise && res_taps && out, RH_ERR_INVALID, "feed_batch_resample: null pointer");
-    const int64_t need = rh_feed_resample_workspace_bytes(n_rows, n_signal, orig_freq, new_freq);
-    RH_REQUIRE(workspace && workspace_bytes >= need, RH_ERR_INVALID, "feed_batch_resample: workspace of %lld bytes, %lld needed",
-               (long long)workspace_bytes, (long long)need);
-    RH_REQUIRE((uintptr_t)workspace % 8 == 0, RH_ERR_INVALID, "feed_batch_resample: workspace is not 8-byte aligned");
-    const int tiles = (p.n_res + kPostTile - 1) / kPostTile;
-    RH_REQUIRE((int64_t)n_rows * tiles <= 0x7fffffffll, RH_ERR_INVALID, "feed_batch_resample: too many tiles for one launch");
-    if (const int rc = feed_check_rows("feed_batch_resample", pcm_samples, rows, taps, n_taps, n_rows, n_signal)) return rc;
-    double* ws = (double*)workspace;
-    double* peaks = ws + (int64_t)n_rows * n_signal;
-    double* ws2 = peaks + n_rows;
-    double* peaks2 = ws2 + (int64_t)n_rows * p.n_res;
-    hipLaunchKernelGGL(feed_pitch_kernel<true>, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, pcm, rows_dev, taps, noise,
-                       n_signal, 1.0 / (double)(1ll << bit_depth), out, ws, peaks);
-    if (const int rc = rh_check_launch("feed_batch_resample")) return rc;
-    if (!normalize && !derivative) {
-        hipLaunchKernelGGL(feed_resample_kernel<false>, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, (const double*)ws, rows_dev,
-                           res_taps, n_signal, p.n_res, p.o, p.n, p.K, p.width, out, (double*)nullptr, (double*)nullptr);
-        return rh_check_launch("feed_batch_resample: resample");
-    }
-    hipLaunchKernelGGL(feed_resample_kernel<true>, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, (const double*)ws, rows_dev,
-                       res_taps, n_signal, p.n_res, p.o, p.n, p.K, p.width, out, ws2, peaks2);
-    if (const int rc = rh_check_launch("feed_batch_resample: resample")) return rc;
-    hipLaunchKernelGGL(feed_post_kernel, dim3(n_rows * tiles), dim3(256), 0, (hipStream_t)stream, (const double*)ws2,
-                       (const double*)peaks2, rows_dev, p.n_res, tiles, n_channels, normalize, max_gain_db, derivative, out);
-    return rh_check_launch("feed_batch_resample: normalize / derivative");
+    return feed_run("feed_batch_post", {pcm, pcm_samples, rows, rows_dev, taps, n_taps, noise, n_rows, n_signal, bit_depth, n_channels,
+                                        normalize, max_gain_db, derivative, orig_freq, new_freq, res_taps, n_res_taps, width, workspace,
+                                        workspace_bytes, out, stream});
 }

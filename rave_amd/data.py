@@ -11,14 +11,14 @@ lmdb / ``AudioExample`` store of scripts/preprocess.py, rave_amd/lmdb_reader.py)
 ``rand_pitch=(lo, hi)`` adds the ``RandomPitch`` that ``rave train --rand_pitch lo,hi`` inserts in front of the crop
 (scripts/train.py:67,169, rave/dataset.py:233-236, rave/transforms.py:56-89: scipy.signal.resample_poly of the whole item by
 a random ratio up / down, padtype='mean') and ``p_mute`` the ``RandomMute`` of rave/configs/augmentations/mute.gin
-(rave/transforms.py:168-177), both in the same launch (rh_feed_batch_pitch_i16_f32): the polyphase filter is evaluated only
+(rave/transforms.py:168-177), both in the same launch (feed_pitch_kernel): the polyphase filter is evaluated only
 for the samples inside the crop window.  ``RandomGain`` (gain.gin) needs nothing: it returns its input unchanged
 (rave/transforms.py:163).  The draws are host logic (``pitch_factors``, ``PitchTable``, ``draw_batch``) and need no GPU.
 
 ``normalize=True`` and ``derivative=True`` are the two steps ``rave train --normalize`` / ``--derivative`` put between
 Dequantize and the augmentations (scripts/train.py:61-63,160-167): ``normalize_signal`` (rave/dataset.py:196-204,241-242: one
 gain per item from the peak over all its channels, capped at ``max_gain_db`` = 30 dB) and the derivator (rave/dataset.py:24-29,
-244-245: ``lfilter([.5, -.5], [1], x)``).  They run in a launch pair (rh_feed_batch_post_i16_f32): the chain kernel keeps its
+244-245: ``lfilter([.5, -.5], [1], x)``).  They run in a launch pair (feed_pitch_kernel, feed_post_kernel): the chain kernel keeps its
 float64 rows and one peak per row in a workspace cached on the feed, a second kernel applies gain and difference in float64 and
 rounds once to float32.
 
@@ -36,11 +36,15 @@ other length scipy pads the item (10000 samples become 10240) or shortens the wi
 dataset's ``metadata.yaml`` rate (``load_lmdb_dataset``: ``info["sr"]``, the ``sr`` of this class) differs from the run's
 (rave/dataset.py:238-239, rave/transforms.py:31-40: torchaudio.functional.resample(x.float(), orig, new) with its defaults).
 torchaudio's filter table is built on the host in float32 as torchaudio builds it (``sinc_resample_kernel``) and kept on the
-device; a launch between the chain kernel and the normalize / derivative kernel (rh_feed_batch_resample_i16_f32) applies it to
+device; a launch between the chain kernel and the normalize / derivative kernel (feed_resample_kernel) applies it to
 the cropped rows, float32 taps times float32 samples summed in float64 and rounded once.  ``sample`` then returns
 ``sinc_resampled_length(n_signal, sr, resample_to)`` samples per row, everything behind Resample (normalize, derivative,
 RandomMute, ``freq_mask`` and its length rule) works on those, and the all-pass keeps the dataset's rate, as in the reference.
 Resample takes no random draws.
+
+A batch with one of these options in play (a ratio, a muted item, a flag, another rate) is ONE call of the widest entry point,
+rh_feed_batch_resample_i16_f32, on the table of ``_row_table``: equal rates switch Resample off, and with neither flag nothing
+follows the chain kernel.  Any other batch is rh_feed_batch_i16_f32 on two columns of the same table.
 
 Not built: ``Compress`` / ``RandomCompress`` (sox ``compand`` through torchaudio, rave/transforms.py:114-145): sox can neither
 be run here nor modelled against anything.
@@ -55,6 +59,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .ops import _twiddle
 
 
 def pole_to_z_filter(omega: float, amplitude: float = .9):
@@ -326,9 +331,8 @@ class GpuBatchFeed:
         bands = check_bands(bands, batch)
         items, in_points, angles = draws[:3]
         ratios = draws[3] if len(draws) > 3 else None
-        n_items, n_ch, length = self.pcm.shape
+        n_ch, dev = self.pcm.shape[1], self.pcm.device
         rows = batch * n_ch
-        dev = self.pcm.device
         if noise is None:
             noise = torch.rand(rows, n_signal, device=dev, generator=self.gen)
         noise = noise.to(dev, torch.float32).contiguous()
@@ -338,79 +342,73 @@ class GpuBatchFeed:
             if self.mask_input is None or self.mask_input.numel() < out.numel():     # regrown only when rows x n_signal grows
                 self.mask_input = torch.empty(out.numel(), device=dev, dtype=torch.float32)
             dst = self.mask_input
+        table = self._row_table(items, in_points, angles, ratios, mute)
         pitched = ratios is not None and any(r is not None for r in ratios)
         muted = mute is not None and any(mute)
-        post = self.normalize or self.derivative
-        if not (pitched or muted or post or self.resample_to is not None):
-            off = np.empty(rows, dtype=np.int64)
-            coef = np.full((rows, 5), np.nan, dtype=np.float64)
-            for b in range(batch):
-                for c in range(n_ch):
-                    r = b * n_ch + c
-                    off[r] = (int(items[b]) * n_ch + c) * length + int(in_points[b])
-                    if angles[b] is not None:
-                        bb, aa = pole_to_z_filter(angles[b], .99)
-                        coef[r] = [bb[0], bb[1], bb[2], aa[1], aa[2]]
-            off_d = torch.from_numpy(off).to(dev)
-            coef_d = torch.from_numpy(coef).to(dev)
+        resample, post = self.resample_to is not None, self.normalize or self.derivative
+        if not (pitched or muted or post or resample):
+            off_d = torch.from_numpy(table["base"] + table["in_point"]).to(dev)
+            coef_d = torch.from_numpy(np.ascontiguousarray(table["coef"])).to(dev)
             L.check(L.lib.rh_feed_batch_i16_f32(L.ptr(self.pcm), L.ptr(off_d), L.ptr(coef_d), L.ptr(noise), rows, n_signal,
                                                 self.bit_depth, L.ptr(dst), L.stream()), "feed_batch")
             return self._mask(dst, out, bands)
-        table = np.zeros(rows, dtype=ROW_DTYPE)
-        table["coef"] = np.nan
-        table["length"] = length
-        table["up"] = table["down"] = 1
-        means = self._means() if pitched else None
-        for b in range(batch):
-            ratio = ratios[b] if ratios is not None else None
-            for c in range(n_ch):
-                row = table[b * n_ch + c]
-                row["base"] = (int(items[b]) * n_ch + c) * length
-                row["in_point"] = int(in_points[b])
-                row["mute"] = int(mute is not None and bool(mute[b]))
-                if angles[b] is not None:
-                    bb, aa = pole_to_z_filter(angles[b], .99)
-                    row["coef"] = [bb[0], bb[1], bb[2], aa[1], aa[2]]
-                if ratio is not None:
-                    row["up"], row["down"] = int(ratio[0]), int(ratio[1])
-                    row["mean"] = means[int(items[b]) * n_ch + c]
-                    row["tap_offset"] = self._tap_offset(ratio)
-        table_d = torch.from_numpy(table.view(np.uint8)).to(dev)
-        n_taps = 0 if self.taps is None else self.taps.numel()
-        if self.resample_to is not None:
-            need = L.lib.rh_feed_resample_workspace_bytes(rows, n_signal, self.sr, self.resample_to)
+        # every other batch is one call of the widest entry point: equal rates switch its Resample stage off, and with neither
+        # flag set nothing follows the chain kernel; ``what`` names the entry point such a call reduces to, as its messages do
+        new = self.resample_to if resample else self.sr
+        what = "feed_batch_resample" if resample else "feed_batch_post" if post else "feed_batch_pitch"
+        ws, ws_bytes = None, 0
+        if resample or post:
+            need = L.lib.rh_feed_resample_workspace_bytes(rows, n_signal, self.sr, new)
             if need < 0:
                 raise RuntimeError(f"GpuBatchFeed: Resample {self.sr} -> {self.resample_to} of {n_signal} samples leaves int32")
-            if self.workspace is None or self.workspace.numel() * 8 < need:
+            if self.workspace is None or self.workspace.numel() * 8 < need:            # regrown only when it must grow
                 self.workspace = torch.empty(need // 8, device=dev, dtype=torch.float64)
-            L.check(L.lib.rh_feed_batch_resample_i16_f32(L.ptr(self.pcm), self.pcm.numel(), table.ctypes.data, L.ptr(table_d),
-                                                         L.ptr(self.taps), n_taps, L.ptr(noise), rows, n_signal, self.bit_depth,
-                                                         n_ch, int(self.normalize), self.max_gain_db, int(self.derivative),
-                                                         self.sr, self.resample_to, L.ptr(self.res_taps), self.res_taps.numel(),
-                                                         self.res_width, L.ptr(self.workspace), self.workspace.numel() * 8,
-                                                         L.ptr(dst), L.stream()), "feed_batch_resample")
-            return self._mask(dst, out, bands)
-        if post:
-            need = L.lib.rh_feed_post_workspace_bytes(rows, n_signal)
-            if self.workspace is None or self.workspace.numel() * 8 < need:            # regrown only when rows x n_signal grows
-                self.workspace = torch.empty(need // 8, device=dev, dtype=torch.float64)
-            L.check(L.lib.rh_feed_batch_post_i16_f32(L.ptr(self.pcm), self.pcm.numel(), table.ctypes.data, L.ptr(table_d),
-                                                     L.ptr(self.taps), n_taps, L.ptr(noise), rows, n_signal, self.bit_depth,
-                                                     n_ch, int(self.normalize), self.max_gain_db, int(self.derivative),
-                                                     L.ptr(self.workspace), self.workspace.numel() * 8, L.ptr(dst), L.stream()),
-                    "feed_batch_post")
-            return self._mask(dst, out, bands)
-        L.check(L.lib.rh_feed_batch_pitch_i16_f32(L.ptr(self.pcm), self.pcm.numel(), table.ctypes.data, L.ptr(table_d),
-                                                  L.ptr(self.taps), n_taps, L.ptr(noise), rows, n_signal, self.bit_depth,
-                                                  L.ptr(dst), L.stream()), "feed_batch_pitch")
+            ws, ws_bytes = self.workspace, self.workspace.numel() * 8
+        table_d = torch.from_numpy(table.view(np.uint8)).to(dev)
+        L.check(L.lib.rh_feed_batch_resample_i16_f32(L.ptr(self.pcm), self.pcm.numel(), table.ctypes.data, L.ptr(table_d),
+                                                     L.ptr(self.taps), 0 if self.taps is None else self.taps.numel(), L.ptr(noise),
+                                                     rows, n_signal, self.bit_depth, n_ch, int(self.normalize), self.max_gain_db,
+                                                     int(self.derivative), self.sr, new, L.ptr(self.res_taps),
+                                                     self.res_taps.numel() if resample else 0, self.res_width if resample else 0,
+                                                     L.ptr(ws), ws_bytes, L.ptr(dst), L.stream()), what)
         return self._mask(dst, out, bands)
+
+    def _row_table(self, items, in_points, angles, ratios, mute) -> np.ndarray:
+        """The ``ROW_DTYPE`` table of a batch, a row per (item, channel): filled per item, repeated over the channels; only
+        ``base`` and ``mean`` differ between the rows of an item.  An item without an angle keeps NaN coefficients (the all-pass
+        missed it), one without a ratio 1/1 and the mean 0, which the kernel then never reads."""
+        _, n_ch, length = self.pcm.shape
+        batch = len(angles)
+        coef = np.full((batch, 5), np.nan)
+        for b, angle in enumerate(angles):
+            if angle is not None:
+                bb, aa = pole_to_z_filter(angle, .99)
+                coef[b] = (bb[0], bb[1], bb[2], aa[1], aa[2])
+        it = np.zeros(batch, dtype=ROW_DTYPE)
+        it["in_point"] = np.asarray(in_points, dtype=np.int64)[:batch]
+        it["coef"] = coef
+        it["length"] = length
+        it["up"] = it["down"] = 1
+        if mute is not None:
+            it["mute"] = np.asarray(mute, dtype=bool)[:batch]
+        pitched = [b for b in range(batch) if ratios[b] is not None] if ratios is not None else []
+        if pitched:
+            it["up"][pitched] = [int(ratios[b][0]) for b in pitched]
+            it["down"][pitched] = [int(ratios[b][1]) for b in pitched]
+            it["tap_offset"][pitched] = [self._tap_offset(ratios[b]) for b in pitched]
+        table = np.repeat(it, n_ch)
+        row = np.repeat(np.asarray(items, dtype=np.int64)[:batch] * n_ch, n_ch) + np.arange(batch * n_ch) % n_ch
+        table["base"] = row * length
+        if pitched:
+            rows = (np.array(pitched)[:, None] * n_ch + np.arange(n_ch)).ravel()        # the table rows of the pitched items
+            table["mean"][rows] = self._means()[row[rows]]
+        return table
 
     def _mask(self, chain_out: torch.Tensor, out: torch.Tensor, bands) -> torch.Tensor:
         """FrequencyMasking of the finished chain: ``chain_out`` (the cached buffer) -> ``out``, every channel of an item with the
         item's band; nothing to do (``chain_out`` is ``out``) when no item of the batch is masked."""
         if bands is None:
             return out
-        from .ops import _twiddle
         batch, n_ch, n_signal = out.shape
         table = np.zeros((batch, n_ch, 2), dtype=np.int32)                             # rows x {first_bin, n_bins}; 0 bins = copy
         for b, band in enumerate(bands):

@@ -162,3 +162,84 @@ def test_entry_point_refuses_on_the_host_table_without_a_launch():
     bad["up"][1] = 20
     assert call(table=bad) != 0 and b"row 1" in L.lib.rh_last_error()
     assert call(rows=0, ws=None, ws_bytes=0) == 0                                                    # no rows: nothing to do
+
+
+class _HostPcm:
+    """Stand-in for the resident PCM (as in tests/test_feed_resample_host.py): a feed looks at its type, shape and device."""
+    dtype, is_cuda, device = torch.int16, True, torch.device("cpu")
+
+    def __init__(self, n_ch):
+        self.shape = (F.N_ITEMS, n_ch, F.LENGTH)
+
+    def dim(self):
+        return 3
+
+    def contiguous(self):
+        return self
+
+
+def _loop_table(D, feed, n_ch, items, in_points, angles, ratios, mute):
+    """The row table as ``GpuBatchFeed.sample`` filled it before ``_row_table``: row by row, field by field."""
+    batch, length = len(items), F.LENGTH
+    table = np.zeros(batch * n_ch, dtype=D.ROW_DTYPE)
+    table["coef"] = np.nan
+    table["length"] = length
+    table["up"] = table["down"] = 1
+    for b in range(batch):
+        ratio = ratios[b] if ratios is not None else None
+        for c in range(n_ch):
+            row = table[b * n_ch + c]
+            row["base"] = (int(items[b]) * n_ch + c) * length
+            row["in_point"] = int(in_points[b])
+            row["mute"] = int(mute is not None and bool(mute[b]))
+            if angles[b] is not None:
+                bb, aa = D.pole_to_z_filter(angles[b], .99)
+                row["coef"] = [bb[0], bb[1], bb[2], aa[1], aa[2]]
+            if ratio is not None:
+                row["up"], row["down"] = int(ratio[0]), int(ratio[1])
+                row["mean"] = feed.means[int(items[b]) * n_ch + c]
+                row["tap_offset"] = feed._tap_offset(ratio)
+    return table
+
+
+def _loop_plain(D, n_ch, items, in_points, angles):
+    """``src_offset`` and ``coef`` of the plain launch as ``sample`` filled them in a loop of their own."""
+    batch, length = len(items), F.LENGTH
+    off = np.empty(batch * n_ch, dtype=np.int64)
+    coef = np.full((batch * n_ch, 5), np.nan, dtype=np.float64)
+    for b in range(batch):
+        for c in range(n_ch):
+            r = b * n_ch + c
+            off[r] = (int(items[b]) * n_ch + c) * length + int(in_points[b])
+            if angles[b] is not None:
+                bb, aa = D.pole_to_z_filter(angles[b], .99)
+                coef[r] = [bb[0], bb[1], bb[2], aa[1], aa[2]]
+    return off, coef
+
+
+@pytest.mark.parametrize("n_ch", [1, 2])
+@pytest.mark.parametrize("with_table", [True, False], ids=["rand_pitch", "no-rand_pitch"])
+def test_row_table_is_the_loop_it_replaces_byte_for_byte(n_ch, with_table):
+    from rave_amd import data as D
+    feed = D.GpuBatchFeed(_HostPcm(n_ch))
+    if with_table:
+        feed.pitch = D.PitchTable(F.PITCH_RANGE)
+    feed.means = np.random.default_rng(11).standard_normal(F.N_ITEMS * n_ch)      # what ``_means`` returns once it is cached
+    mute = np.array([False, True, True, False, False, True])
+    # (1, 19) and (0, 5) are outside every table: sentinel -1; (3, 3) reduces to 1/1: sentinel 0 with a table, -1 without
+    odd = [(13, 10), (1, 19), (3, 3), None, (0, 5), (14, 19)]
+    for ratios in (None, [None] * F.N_ITEMS, F.RATIOS, odd):
+        for m in (None, mute, list(mute), [False] * F.N_ITEMS):
+            for items, in_points, angles in ((F.ITEMS, F.IN_POINTS, F.ANGLES), (F.ITEMS[::-1], F.PITCH_IN_POINTS, F.ANGLES_FLIPPED),
+                                             (list(F.ITEMS), list(F.IN_POINTS), [None] * F.N_ITEMS)):
+                got = feed._row_table(items, in_points, angles, ratios, m)
+                want = _loop_table(D, feed, n_ch, items, in_points, angles, ratios, m)
+                assert got.dtype == want.dtype == D.ROW_DTYPE and got.shape == want.shape == (F.N_ITEMS * n_ch,)
+                assert got.tobytes() == want.tobytes(), (ratios, m, angles)
+                off, coef = _loop_plain(D, n_ch, items, in_points, angles)
+                src_offset, table_coef = got["base"] + got["in_point"], np.ascontiguousarray(got["coef"])
+                assert src_offset.dtype == off.dtype and src_offset.tobytes() == off.tobytes()
+                assert table_coef.dtype == coef.dtype and table_coef.shape == coef.shape and table_coef.tobytes() == coef.tobytes()
+    taps = feed._row_table(F.ITEMS, F.PITCH_IN_POINTS, F.ANGLES, odd, None)["tap_offset"][::n_ch]
+    assert list(taps[[1, 2, 3, 4]]) == ([-1, 0, 0, -1] if with_table else [-1, -1, 0, -1])
+    assert (taps[0] >= 0 and taps[5] > 0 and taps[0] != taps[5]) if with_table else (taps[0] == taps[5] == -1)

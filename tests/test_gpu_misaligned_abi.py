@@ -981,7 +981,7 @@ def _feed_reference(pcm, noise, items, in_points, ratios, dtype):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("pitched", [False, True], ids=["rh_feed_batch_i16_f32", "rh_feed_batch_pitch_i16_f32"])
+@pytest.mark.parametrize("pitched", [False, True], ids=["rh_feed_batch_i16_f32", "rh_feed_batch_resample_i16_f32"])
 def test_batch_feed_with_noise_and_out_misaligned(dev, pitched):
     """3 rows x 2048 samples of the data feed with ``noise`` and / or ``out`` 1, 2, 3 floats off a 16-byte boundary, against the
     reference's chain restated with scipy (float64): the bound of test_gpu_batch_feed_matches_the_reference_transform_chain
@@ -998,7 +998,7 @@ def test_batch_feed_with_noise_and_out_misaligned(dev, pitched):
     in_points = np.array([0, 777, n_res[2] - FEED_N])
     feed = D.GpuBatchFeed(torch.from_numpy(pcm).to(dev), sr=44100, seed=1, **(dict(rand_pitch=(0.6, 1.4)) if pitched else {}))
     draws = (items, in_points, FEED_ANGLES, ratios) if pitched else (items, in_points, FEED_ANGLES)
-    name, index = ("rh_feed_batch_pitch_i16_f32", 10) if pitched else ("rh_feed_batch_i16_f32", 7)
+    name, index = ("rh_feed_batch_resample_i16_f32", 21) if pitched else ("rh_feed_batch_i16_f32", 7)
     ref64 = _feed_reference(pcm, noise, items, in_points, ratios, np.float64)
     own = np.abs(_feed_reference(pcm, noise, items, in_points, ratios, np.float32).astype(np.float32) - ref64).max(1) if pitched \
         else np.zeros(3)

@@ -1,6 +1,6 @@
 """Throughput of the GPU data feed (rave_amd/data.py): batches of 32 x 65536 from 64 resident items.
 ``--rand-pitch lo,hi`` adds a leg with RandomPitch on (about half the items resampled), ``--post`` a leg with ``normalize``
-and ``derivative`` on (rh_feed_batch_post_i16_f32: the chain kernel plus the gain / difference kernel), ``--freq_mask P`` two
+and ``derivative`` on (the launches of rh_feed_batch_post_i16_f32: the chain kernel plus the gain / difference kernel), ``--freq_mask P`` two
 legs with FrequencyMasking on (rh_feed_freq_mask_f32 behind the chain: every item masked, and a share P of them),
 ``--resample ORIG,NEW`` a leg with Resample(ORIG, NEW) behind Dequantize (rh_feed_batch_resample_i16_f32: the chain kernel plus the
 resampling kernel; with ``--post`` a second one with ``normalize`` and ``derivative`` behind it, three launches), ``--step`` the
