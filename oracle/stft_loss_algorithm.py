@@ -11,7 +11,7 @@ PLANS = {128: [8, 8, 2], 256: [8, 8, 4], 512: [8, 8, 8], 1024: [8, 8, 8, 2], 204
 def stockham_fft(z):
     """Forward DFT of a length-n complex vector with the kernel's pass structure: n/8 "threads" holding 8 points each;
     butterfly j = t + u n/8 of a radix-R pass takes in[j + r n/R], twiddles by exp(-2 pi i r k / (NS R)), k = j mod NS, and
-    writes (j - k) R + k + r NS (stft_loss.hip: Fft<N>::load / store8)."""
+    writes (j - k) R + k + r NS (fft_lds.inc: Fft<N>::load / store8)."""
     n = len(z)
     tw = np.exp(-2j * np.pi * np.arange(n) / n)
     tpf, buf, ns = n // 8, np.asarray(z, dtype=complex).copy(), 1

@@ -13,10 +13,9 @@
 //   * a workgroup owns one hop block b of one row and transforms both frames that cover it, b and b + 1: twice the arithmetic
 //     of a frame-per-workgroup scheme, but one launch, no scratch in HBM, no atomics, and every output sample has one writer and
 //     one fixed order of operations, whatever the grid.
-//   * the 4096-point real transform of a frame is ONE 2048-point complex transform of z[m] = u[2m] + i u[2m + 1] on the in-LDS
-//     FFT of stft_loss.hip / mel.hip (fft_lds.inc, 256 threads, 8 points each).  With Z its spectrum, M = 2048, W = e^{-2 pi i / 4096}:
-//       E_k = (Z_k + conj Z_{M-k}) / 2,  O_k = (Z_k - conj Z_{M-k}) / 2i,  U_k = E_k + W^k O_k,  U_{M-k} = conj(E_k - W^k O_k)
-//     and the packed spectrum of the real signal with the one-sided spectrum V = B . U is
+//   * the 4096-point real transform of a frame is ONE 2048-point complex transform on the packed scheme of fft_lds.inc (256
+//     threads, 8 points each).  With Z, E, O, U, W and M = 2048 as there, the packed spectrum of the real signal with the
+//     one-sided spectrum V = B . U is
 //       Zi_k = (V_k + conj V_{M-k}) / 2 + i W^{-k} (V_k - conj V_{M-k}) / 2
 //            = s Z_k + d (W^k O_k + i W^{-k} E_k),     s = (B_k + B_{M-k}) / 2,  d = (B_k - B_{M-k}) / 2
 //     (B_M = 0: the band never holds the Nyquist bin), zero wherever neither k nor M - k is in the band.  Forward split and
@@ -88,8 +87,8 @@ __global__ __launch_bounds__(256) void feed_mask_kernel(const float* __restrict_
             c32 zi = mk(0.f, 0.f);
             if (bk || bm) {
                 const c32 zk = z[zpad(k)], zm = z[zpad(km & (kMaskHop - 1))];
-                const c32 e = mk(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
-                const c32 o = mk(0.5f * (zk.y + zm.y), 0.5f * (zm.x - zk.x));
+                c32 e, o;
+                pair_split(zk, zm, 0.5f, 0.5f, e, o);
                 const c32 wo = cmul(o, wk[q]), we = cmul(e, mk(wk[q].x, -wk[q].y));
                 const float sc = bk && bm ? 1.f : 0.5f, dc = bk && bm ? 0.f : (bk ? 0.5f : -0.5f);
                 zi = zk * sc + mk(wo.x - we.y, wo.y + we.x) * dc;
@@ -124,7 +123,7 @@ extern "C" int rh_feed_freq_mask_f32(const float* x, float* y, const int32_t* ba
     RH_REQUIRE(n_signal >= 2 * kMaskHop && n_signal % kMaskHop == 0, RH_ERR_INVALID,
                "feed_freq_mask: n_signal %d is not a multiple of %d of at least %d (scipy.signal.stft would pad the item)", n_signal,
                kMaskHop, 2 * kMaskHop);
-    RH_REQUIRE((reinterpret_cast<uintptr_t>(twiddle) & 7) == 0, RH_ERR_INVALID, "feed_freq_mask: the twiddle table must be 8-byte aligned");
+    if (const int rc = check_twiddle("feed_freq_mask", twiddle)) return rc;
     const int64_t n_blocks = n_signal / kMaskHop;
     RH_REQUIRE(n_rows * n_blocks <= 0x7fffffffll, RH_ERR_INVALID, "feed_freq_mask: too many hop blocks for one launch");
     const uintptr_t xa = reinterpret_cast<uintptr_t>(x), ya = reinterpret_cast<uintptr_t>(y);

@@ -1,7 +1,21 @@
-// The in-LDS complex FFT shared by stft_loss.hip, mel.hip and feed_mask.hip (N = 128 ... 2048; Stockham autosort, radix 8 +
-// one radix 2 / 4 pass, N / 8 threads per transform, 256 / (N / 8) transforms per workgroup side by side), the reflect index
-// of a centred frame and the power-of-two equaliser of a frame pair.  Included INSIDE the including file's anonymous namespace,
-// after common.hpp; see the header of stft_loss.hip for the scheme.
+// The frame-pair FFT stage of stft_loss.hip, mel.hip, spectrogram.hip and feed_mask.hip.  Included INSIDE the including file's
+// anonymous namespace, after common.hpp; the device pieces come first, the host's checks and size dispatcher last.
+//
+//   * the transform: an in-LDS complex FFT, N = 128 ... 2048.  Stockham autosort, radix 8 (+ one radix 2 / 4 pass), N / 8 threads per
+//     transform holding 8 points each, 256 / (N / 8) transforms per workgroup side by side; the LDS image is padded by one slot per
+//     8 (zpad) so that the stride-8 stores of the first pass are conflict free; twiddles from a host-made table (f64 -> f32).
+//   * the pair scheme: two real frames ride one transform as z = w (x + i y) and are split by X_k = (Z_k + conj Z_{n-k}) / 2,
+//     Y_k = (Z_k - conj Z_{n-k}) / 2i (pair_split; each kernel walks the bin pairs itself).
+//   * the equaliser (frame_scale, round 5): the two frames of a pair are EQUALISED first, y enters as s y with s = 2^(exponent of
+//     max |x| over the frame - exponent of max |y|), exact in floating point, and Y = Y' / s after the transform.  A transform's
+//     rounding error is ~ 1e-7 of the norm of its WHOLE input, so without this the quieter signal inherits the louder one's noise:
+//     at the start of training the decoder's output is ~ 50x below the target and d log(|Y| + 1e-7) turned that noise into a
+//     multiband gradient 60 % off the f64 value, where torch's separate f32 transforms are 0.3 % off
+//     (profiles/round5_stft_pair_equalisation.txt); likewise the quiet frame of a pair at an onset (tests/test_gpu_mel.py).
+//   * the packed scheme: a real frame u of 2 M = 4096 points is ONE M-point transform of z[m] = u[2m] + i u[2m + 1] (twiddles
+//     from the 4096-point table: Tw::init<2>).  With Z its spectrum and W = e^{-2 pi i / 2M}: E_k = (Z_k + conj Z_{M-k}) / 2,
+//     O_k = (Z_k - conj Z_{M-k}) / 2i (pair_split again: the even and the odd samples are the pair), U_k = E_k + W^k O_k,
+//     U_{M-k} = conj(E_k - W^k O_k).
 
 typedef float c32 __attribute__((ext_vector_type(2)));       // complex as a packed pair: adds / twiddle products are v_pk_* ops
 
@@ -50,6 +64,69 @@ __device__ __forceinline__ void dft(c32* v) {
 }
 
 __device__ __forceinline__ int zpad(int i) { return i + (i >> 3); }
+
+__device__ __forceinline__ int reflect_at(int p, int t) { return p < 0 ? -p : (p >= t ? 2 * (t - 1) - p : p); }
+
+// the 8 samples n = t + r N/8 of frames f (-> .x) and f + 1 (-> .y) of one row, frame f starting at f hop - off; zero for a
+// frame the workgroup does not own
+template <int N>
+__device__ __forceinline__ void load_pair(c32 (&v)[8], const float* __restrict__ xr, int t_len, int hop, int off, int f, bool va,
+                                          bool vb, int t) {
+    constexpr int TPF = N / 8;
+    const int p0 = f * hop - off + t;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const int q = p0 + r * TPF;
+        const float a = va ? xr[reflect_at(q, t_len)] : 0.f;
+        const float b = vb ? xr[reflect_at(q + hop, t_len)] : 0.f;
+        v[r] = mk(a, b);
+    }
+}
+
+// The pair split: X = hx (Z_k + conj Z_{n-k}), Y = hy (Z_k - conj Z_{n-k}) / i from z1 = Z_k, z2 = Z_{n-k}.  hx = 1/2 and
+// hy = 1/2 x the equaliser's inverse give the two spectra; a caller's own scale goes INTO the prefactors (its rounding).
+__device__ __forceinline__ void pair_split(c32 z1, c32 z2, float hx, float hy, c32& X, c32& Y) {
+    X = mk(hx * (z1.x + z2.x), hx * (z1.y - z2.y));
+    Y = mk(hy * (z1.y + z2.y), hy * (z2.x - z1.x));
+}
+
+// Equaliser of a frame pair: s = 2^(e_x - e_y) from the largest |x| and |y| of the frame (all N samples: the TPF threads of
+// the transform; across waves through `fmx`, one slot per wave -- the barriers inside the transform that follows separate this
+// read from the next frame's write), 1 when either frame is all zero.  Every thread of the workgroup must call it.
+template <int TPF>
+__device__ __forceinline__ void frame_scale(const c32 (&vn)[8], c32* fmx, float& s, float& inv_s, int on) {
+    float mx = 0.f, my = 0.f;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        mx = fmaxf(mx, fabsf(vn[r].x));
+        my = fmaxf(my, fabsf(vn[r].y));
+    }
+    constexpr int W = TPF < 64 ? TPF : 64;
+#pragma unroll
+    for (int o = W / 2; o >= 1; o >>= 1) {
+        mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+        my = fmaxf(my, __shfl_xor(my, o, 64));
+    }
+    if (TPF > 64) {
+        const int wave = threadIdx.x >> 6;
+        if ((threadIdx.x & 63) == 0) fmx[wave] = mk(mx, my);
+        __syncthreads();
+        const int w0 = (threadIdx.x / TPF) * (TPF / 64);
+        mx = my = 0.f;
+#pragma unroll
+        for (int i = 0; i < TPF / 64; ++i) {
+            const c32 q = fmx[w0 + i];
+            mx = fmaxf(mx, q.x);
+            my = fmaxf(my, q.y);
+        }
+    }
+    int d = (mx > 0.f && my > 0.f) ? (int)(__float_as_uint(mx) >> 23) - (int)(__float_as_uint(my) >> 23) : 0;
+    d = d < -100 ? -100 : (d > 100 ? 100 : d);
+    if (!on) d = 0;
+    if (TPF >= 64) d = __builtin_amdgcn_readfirstlane(d);      // a whole wave works on one transform: the scale lives in an SGPR
+    s = __uint_as_float((unsigned)(127 + d) << 23);
+    inv_s = __uint_as_float((unsigned)(127 - d) << 23);
+}
 
 template <int N>
 struct Fft {
@@ -158,42 +235,32 @@ struct Fft {
     }
 };
 
-__device__ __forceinline__ int reflect_at(int p, int t) { return p < 0 ? -p : (p >= t ? 2 * (t - 1) - p : p); }
+// ---------------------------------------------------------------------------------------------------------------- host
+// a built transform size up to `max_n` (2048, or 4096 where the unit has the packed scheme)
+bool fft_size_ok(int n, int max_n) { return n >= 128 && n <= max_n && (n & (n - 1)) == 0; }
 
-// Equaliser of a frame pair: s = 2^(e_x - e_y) from the largest |x| and |y| of the frame (all N samples: the TPF threads of
-// the transform; across waves through `fmx`, one slot per wave -- the barriers inside the transform that follows separate this
-// read from the next frame's write), 1 when either frame is all zero.  Every thread of the workgroup must call it.
-template <int TPF>
-__device__ __forceinline__ void frame_scale(const c32 (&vn)[8], c32* fmx, float& s, float& inv_s, int on) {
-    float mx = 0.f, my = 0.f;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        mx = fmaxf(mx, fabsf(vn[r].x));
-        my = fmaxf(my, fabsf(vn[r].y));
+// fn(FftSize<n_fft>()) with the size as a compile-time constant; the caller has checked fft_size_ok(n_fft, MAX)
+template <int N>
+struct FftSize { static constexpr int value = N; };
+template <int MAX, class Fn>
+int fft_dispatch(int n_fft, Fn fn) {
+    switch (n_fft) {
+        case 128: return fn(FftSize<128>());
+        case 256: return fn(FftSize<256>());
+        case 512: return fn(FftSize<512>());
+        case 1024: return fn(FftSize<1024>());
+        case 2048: return fn(FftSize<2048>());
+        default: return fn(FftSize<MAX>());      // 4096 where built; never another size: the caller's fft_size_ok
     }
-    constexpr int W = TPF < 64 ? TPF : 64;
-#pragma unroll
-    for (int o = W / 2; o >= 1; o >>= 1) {
-        mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-        my = fmaxf(my, __shfl_xor(my, o, 64));
-    }
-    if (TPF > 64) {
-        const int wave = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) fmx[wave] = mk(mx, my);
-        __syncthreads();
-        const int w0 = (threadIdx.x / TPF) * (TPF / 64);
-        mx = my = 0.f;
-#pragma unroll
-        for (int i = 0; i < TPF / 64; ++i) {
-            const c32 q = fmx[w0 + i];
-            mx = fmaxf(mx, q.x);
-            my = fmaxf(my, q.y);
-        }
-    }
-    int d = (mx > 0.f && my > 0.f) ? (int)(__float_as_uint(mx) >> 23) - (int)(__float_as_uint(my) >> 23) : 0;
-    d = d < -100 ? -100 : (d > 100 ? 100 : d);
-    if (!on) d = 0;
-    if (TPF >= 64) d = __builtin_amdgcn_readfirstlane(d);      // a whole wave works on one transform: the scale lives in an SGPR
-    s = __uint_as_float((unsigned)(127 + d) << 23);
-    inv_s = __uint_as_float((unsigned)(127 - d) << 23);
+}
+
+// the twiddle table is read as c32; `what` (the operation's name) leads the message
+int check_twiddle(const char* what, const void* twiddle) {
+    RH_REQUIRE(twiddle && (reinterpret_cast<uintptr_t>(twiddle) & 7) == 0, RH_ERR_INVALID,
+               "%s: the twiddle table must be non-null and 8-byte aligned", what);
+    return RH_OK;
+}
+int check_scale(const char* what, float scale) {
+    RH_REQUIRE(scale > 0.f && scale <= 3.4e38f, RH_ERR_INVALID, "%s: scale must be a positive finite number", what);
+    return RH_OK;
 }

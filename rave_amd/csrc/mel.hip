@@ -4,11 +4,9 @@
 // y (rows, n_mels, frames), so that a plain reshape gives the encoder's (B, n_channels * n_mels, frames).  A frame lives in LDS
 // from the windowed load to the mel sums: HBM traffic = the waveform read (4x-8x overlapped, from L2) + the result written.
 //
-//   * frames are indexed straight from x (reflect_at: no padded copy) and transformed in PAIRS, frames f and f + 1 of one row
-//     as z = w (a + i b) on the in-LDS FFT of stft_loss.hip (fft_lds.inc), split by X_k = (Z_k + conj Z_{n-k}) / 2,
-//     Y_k = (Z_k - conj Z_{n-k}) / 2i.  The pair is EQUALISED by a power of two first (frame_scale, exact): a transform's rounding
-//     error is ~ 1e-7 of the norm of its WHOLE input, so at an onset the quiet frame of a pair would inherit the loud one's noise
-//     (profiles/round5_stft_pair_equalisation.txt; tests/test_gpu_mel.py pins it).
+//   * frames are indexed straight from x (reflect_at: no padded copy) and transformed in PAIRS, frames f and f + 1 of one row,
+//     equalised by a power of two: at an onset the quiet frame of a pair would otherwise inherit the loud one's noise
+//     (tests/test_gpu_mel.py pins it).  fft_lds.inc has the transform, the pair scheme and the equaliser.
 //   * the power spectra of the pair go to LDS; filter m walks its own bin range [lo_m, hi_m) from a small table, weights from the
 //     module's `fb` buffer (no bin feeds more than two filters: ~2 (n/2 + 1) products per frame instead of (n/2 + 1) n_mels), in
 //     ascending bin order: no atomics, the same bits from run to run.
@@ -44,21 +42,6 @@ struct MelP {
     float scale;             // 1 / sum(window^2) (normalized) or 1
 };
 
-// the 8 samples n = t + r n/8 of frames f (-> .x) and f + 1 (-> .y) of one row, zero for a frame the workgroup does not own
-template <int N>
-__device__ __forceinline__ void load_pair(c32 (&v)[8], const float* __restrict__ xr, int t_len, int hop, int f, bool va, bool vb,
-                                          int t) {
-    constexpr int TPF = N / 8;
-    const int p0 = f * hop - N / 2 + t;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const int q = p0 + r * TPF;
-        const float a = va ? xr[reflect_at(q, t_len)] : 0.f;
-        const float b = vb ? xr[reflect_at(q + hop, t_len)] : 0.f;
-        v[r] = mk(a, b);
-    }
-}
-
 template <int N>
 __global__ __launch_bounds__(256) void mel_fwd_kernel(const MelP p) {
     typedef Fft<N> F;
@@ -86,13 +69,13 @@ __global__ __launch_bounds__(256) void mel_fwd_kernel(const MelP p) {
     const int n_mels = p.n_mels;
     float sc = 1.f, isc = 1.f;       // equaliser of the current pair and its inverse (frame_scale)
     auto bin = [&](int k, c32 z1, c32 z2) {
-        const float ar = 0.5f * (z1.x + z2.x), ai = 0.5f * (z1.y - z2.y);
-        const float br = (0.5f * isc) * (z1.y + z2.y), bi = (0.5f * isc) * (z2.x - z1.x);
-        pa[k] = (ar * ar + ai * ai) * scale;
-        pb[k] = (br * br + bi * bi) * scale;
+        c32 A, B;
+        pair_split(z1, z2, 0.5f, 0.5f * isc, A, B);
+        pa[k] = (A.x * A.x + A.y * A.y) * scale;
+        pb[k] = (B.x * B.x + B.y * B.y) * scale;
     };
     c32 vn[8];
-    load_pair<N>(vn, xr, p.t_len, p.hop, f0 + 2 * gi, f0 + 2 * gi < f1, f0 + 2 * gi + 1 < f1, t);
+    load_pair<N>(vn, xr, p.t_len, p.hop, N / 2, f0 + 2 * gi, f0 + 2 * gi < f1, f0 + 2 * gi + 1 < f1, t);
     for (int fr = f0; fr < f0 + M::FPW; fr += M::FPR) {          // the same trip count for every thread (barriers inside)
         const int fa = fr + 2 * gi;
         c32 v[8];
@@ -100,7 +83,7 @@ __global__ __launch_bounds__(256) void mel_fwd_kernel(const MelP p) {
 #pragma unroll
         for (int r = 0; r < 8; ++r) v[r] = mk(vn[r].x, vn[r].y * sc) * wn[r];
         // the next round's samples fly under this one's passes
-        load_pair<N>(vn, xr, p.t_len, p.hop, fa + M::FPR, fa + M::FPR < f1, fa + M::FPR + 1 < f1, t);
+        load_pair<N>(vn, xr, p.t_len, p.hop, N / 2, fa + M::FPR, fa + M::FPR < f1, fa + M::FPR + 1 < f1, t);
         F::run(v, z, t, tw);
         F::store_natural(v, z, t);
         {
@@ -135,10 +118,8 @@ __global__ __launch_bounds__(256) void mel_fwd_kernel(const MelP p) {
     }
 }
 
-bool n_fft_ok(int n) { return n == 128 || n == 256 || n == 512 || n == 1024 || n == 2048; }
-
 bool mel_shape_ok(int n_fft, int hop, int n_mels, int t_len, long rows) {
-    return n_fft_ok(n_fft) && hop >= 1 && hop <= n_fft && n_mels >= 1 && n_mels <= kMelMax && t_len > n_fft / 2 && t_len >= hop &&
+    return fft_size_ok(n_fft, 2048) && hop >= 1 && hop <= n_fft && n_mels >= 1 && n_mels <= kMelMax && t_len > n_fft / 2 && t_len >= hop &&
            (long)t_len + 80l * n_fft < 0x7fffffffl && rows > 0 && rows < 65536;      // (frame index x hop stays an int one
                                                                                       // workgroup's frames past the end)
 }
@@ -164,17 +145,11 @@ extern "C" int rh_mel_fwd_f32(const float* x, const float* window, const float* 
                "mel_fwd: unsupported geometry (n_fft %d, hop %d, n_mels %d, t %d, rows %lld)", n_fft, hop, n_mels, t_len, (long long)rows);
     RH_REQUIRE(n_frames == t_len / hop || n_frames == t_len / hop + 1, RH_ERR_INVALID,
                "mel_fwd: n_frames %d is neither t / hop nor t / hop + 1 (t %d, hop %d)", n_frames, t_len, hop);
-    RH_REQUIRE((reinterpret_cast<uintptr_t>(twiddle) & 7) == 0, RH_ERR_INVALID, "mel_fwd: the twiddle table must be 8-byte aligned");
-    RH_REQUIRE(scale > 0.f && scale <= 3.4e38f, RH_ERR_INVALID, "mel_fwd: scale must be a positive finite number");
+    if (const int rc = check_twiddle("mel_fwd", twiddle)) return rc;
+    if (const int rc = check_scale("mel_fwd", scale)) return rc;
     RH_REQUIRE(rows * (int64_t)n_mels * n_frames < (int64_t)1 << 40, RH_ERR_UNSUPPORTED, "mel_fwd: output too large");
     MelP p = {};
     p.x = x; p.win = window; p.tw = reinterpret_cast<const c32*>(twiddle); p.fb = fb; p.bins = bins; p.y = y;
     p.t_len = t_len; p.hop = hop; p.n_frames = n_frames; p.n_mels = n_mels; p.log1p = log1p ? 1 : 0; p.scale = scale;
-    switch (n_fft) {
-        case 128: return launch_mel<128>(p, (int)rows, (hipStream_t)stream);
-        case 256: return launch_mel<256>(p, (int)rows, (hipStream_t)stream);
-        case 512: return launch_mel<512>(p, (int)rows, (hipStream_t)stream);
-        case 1024: return launch_mel<1024>(p, (int)rows, (hipStream_t)stream);
-        default: return launch_mel<2048>(p, (int)rows, (hipStream_t)stream);
-    }
+    return fft_dispatch<2048>(n_fft, [&](auto n) { return launch_mel<decltype(n)::value>(p, (int)rows, (hipStream_t)stream); });
 }

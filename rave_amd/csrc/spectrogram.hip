@@ -7,10 +7,8 @@
 // (real, imag) planes written frame-minor.  rows = batch * channels; plane p of row (b, c) is channel p * channels + c of batch
 // b in out (batch, 2 channels, bins, frames): the reference's cat([real, imag], 1) itself; with channels = 1 out is
 // (rows, 2, bins, frames).
-//   * n_fft <= 2048: frames f and f + 1 of a row as z = w (a + i b) on the in-LDS FFT of fft_lds.inc, split by
-//     X_k = (Z_k + conj Z_{n-k}) / 2, Y_k = (Z_k - conj Z_{n-k}) / 2i, the pair equalised by a power of two first
-//     (frame_scale, as in mel.hip).  n_fft = 4096: one frame as the 2048-point transform of z[m] = u[2m] + i u[2m+1], merged
-//     by U_k = E_k + W^k O_k (the scheme of feed_mask.hip).
+//   * n_fft <= 2048: frames f and f + 1 of a row as one equalised pair; n_fft = 4096: one frame on the packed scheme
+//     (fft_lds.inc has the transform and both schemes).
 //   * a workgroup owns FPW consecutive frames of a row and collects both planes in an LDS tile [plane][bin][frame]; the
 //     tile leaves in runs of FPW consecutive frames per bin (float4 where `out` and the frame count allow it).
 //
@@ -117,21 +115,6 @@ __device__ __forceinline__ bool vec_ok(const void* p, int n_frames) {
 }
 
 // ------------------------------------------------------------------------------------------------------------- forward
-// the 8 samples n = t + r n/8 of frames f (-> .x) and f + 1 (-> .y) of one row, zero for a frame the workgroup does not own
-template <int N>
-__device__ __forceinline__ void load_pair(c32 (&v)[8], const float* __restrict__ xr, int t_len, int hop, int off, int f, bool va,
-                                          bool vb, int t) {
-    constexpr int TPF = N / 8;
-    const int p0 = f * hop - off + t;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const int q = p0 + r * TPF;
-        const float a = va ? xr[reflect_at(q, t_len)] : 0.f;
-        const float b = vb ? xr[reflect_at(q + hop, t_len)] : 0.f;
-        v[r] = mk(a, b);
-    }
-}
-
 template <int N>
 __global__ __launch_bounds__(256) void spec_fwd_kernel(const SpecP p) {
     typedef SpecGeom<N> S;
@@ -157,10 +140,12 @@ __global__ __launch_bounds__(256) void spec_fwd_kernel(const SpecP p) {
     float sc = 1.f, isc = 1.f;       // equaliser of the current pair and its inverse (frame_scale)
     float* ta = tile;
     auto bin = [&](int k, c32 z1, c32 z2) {
-        ta[k * TS] = (0.5f * scale) * (z1.x + z2.x);
-        ta[(NB + k) * TS] = (0.5f * scale) * (z1.y - z2.y);
-        ta[k * TS + 1] = (0.5f * scale * isc) * (z1.y + z2.y);
-        ta[(NB + k) * TS + 1] = (0.5f * scale * isc) * (z2.x - z1.x);
+        c32 A, B;
+        pair_split(z1, z2, 0.5f * scale, 0.5f * scale * isc, A, B);
+        ta[k * TS] = A.x;
+        ta[(NB + k) * TS] = A.y;
+        ta[k * TS + 1] = B.x;
+        ta[(NB + k) * TS + 1] = B.y;
     };
     c32 vn[8];
     load_pair<N>(vn, xr, p.t_len, p.hop, off, f0 + 2 * gi, f0 + 2 * gi < f1, f0 + 2 * gi + 1 < f1, t);
@@ -235,8 +220,8 @@ __global__ __launch_bounds__(256) void spec_fwd4096_kernel(const SpecP p) {
         for (int q = 0; q < 8; ++q) {
             const int k = t + 256 * q;
             const c32 zk = z[zpad(k)], zm = z[zpad((M - k) & (M - 1))];
-            const c32 e = mk(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));
-            const c32 o = mk(0.5f * (zk.y + zm.y), 0.5f * (zm.x - zk.x));
+            c32 e, o;
+            pair_split(zk, zm, 0.5f, 0.5f, e, o);
             const c32 u = e + cmul(o, wk[q]);
             tile[k * TS + j] = u.x * scale;
             tile[(NB + k) * TS + j] = u.y * scale;
@@ -375,10 +360,8 @@ __global__ __launch_bounds__(256) void spec_bwd_kernel(const SpecP p) {
     }
 }
 
-bool n_fft_ok(int n) { return n >= 128 && n <= 4096 && (n & (n - 1)) == 0; }
-
 bool spec_shape_ok(int n_fft, int hop, int t_len, long rows, int center) {
-    return n_fft_ok(n_fft) && hop >= 1 && hop <= n_fft && (center ? t_len > n_fft / 2 : t_len >= n_fft) &&
+    return fft_size_ok(n_fft, 4096) && hop >= 1 && hop <= n_fft && (center ? t_len > n_fft / 2 : t_len >= n_fft) &&
            t_len <= (1 << 30) && rows > 0 && rows < 65536;
     // t_len <= 2^30: the backward's mirror index 2 (T - 1) and the forward's look-ahead (two tiles of frames past the last one,
     // under 2^15 samples at any built size) stay inside an int
@@ -409,8 +392,8 @@ int check_common(const char* what, const void* a, const void* window, const void
                center);
     RH_REQUIRE(channels >= 1 && rows % channels == 0, RH_ERR_INVALID, "%s: %lld rows are no multiple of %d channels", what,
                (long long)rows, channels);
-    RH_REQUIRE((reinterpret_cast<uintptr_t>(twiddle) & 7) == 0, RH_ERR_INVALID, "%s: the twiddle table must be 8-byte aligned", what);
-    RH_REQUIRE(scale > 0.f && scale <= 3.4e38f, RH_ERR_INVALID, "%s: scale must be a positive finite number", what);
+    if (const int rc = check_twiddle(what, twiddle)) return rc;
+    if (const int rc = check_scale(what, scale)) return rc;
     RH_REQUIRE(rows * (int64_t)(n_fft + 2) * frames_of(n_fft, hop, t_len, center) < (int64_t)1 << 40, RH_ERR_UNSUPPORTED,
                "%s: output too large", what);
     return RH_OK;
@@ -431,14 +414,7 @@ extern "C" int rh_spectrogram_fwd_f32(const float* x, const float* window, const
     p.x = x; p.win = window; p.tw = reinterpret_cast<const c32*>(twiddle); p.out = out;
     p.t_len = t_len; p.hop = hop; p.center = center ? 1 : 0; p.channels = channels; p.scale = scale;
     p.n_frames = frames_of(n_fft, hop, t_len, p.center);
-    switch (n_fft) {
-        case 128: return launch_fwd<128>(p, (int)rows, (hipStream_t)stream);
-        case 256: return launch_fwd<256>(p, (int)rows, (hipStream_t)stream);
-        case 512: return launch_fwd<512>(p, (int)rows, (hipStream_t)stream);
-        case 1024: return launch_fwd<1024>(p, (int)rows, (hipStream_t)stream);
-        case 2048: return launch_fwd<2048>(p, (int)rows, (hipStream_t)stream);
-        default: return launch_fwd<4096>(p, (int)rows, (hipStream_t)stream);
-    }
+    return fft_dispatch<4096>(n_fft, [&](auto n) { return launch_fwd<decltype(n)::value>(p, (int)rows, (hipStream_t)stream); });
 }
 
 extern "C" int rh_spectrogram_bwd_f32(const float* dout, const float* window, const float* twiddle, int64_t rows, int32_t channels,
@@ -450,12 +426,5 @@ extern "C" int rh_spectrogram_bwd_f32(const float* dout, const float* window, co
     p.dout = dout; p.win = window; p.tw = reinterpret_cast<const c32*>(twiddle); p.dx = dx;
     p.t_len = t_len; p.hop = hop; p.center = center ? 1 : 0; p.channels = channels; p.scale = scale;
     p.n_frames = frames_of(n_fft, hop, t_len, p.center);
-    switch (n_fft) {
-        case 128: return launch_bwd<128>(p, (int)rows, (hipStream_t)stream);
-        case 256: return launch_bwd<256>(p, (int)rows, (hipStream_t)stream);
-        case 512: return launch_bwd<512>(p, (int)rows, (hipStream_t)stream);
-        case 1024: return launch_bwd<1024>(p, (int)rows, (hipStream_t)stream);
-        case 2048: return launch_bwd<2048>(p, (int)rows, (hipStream_t)stream);
-        default: return launch_bwd<4096>(p, (int)rows, (hipStream_t)stream);
-    }
+    return fft_dispatch<4096>(n_fft, [&](auto n) { return launch_bwd<decltype(n)::value>(p, (int)rows, (hipStream_t)stream); });
 }

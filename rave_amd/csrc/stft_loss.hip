@@ -6,17 +6,9 @@
 // partial sums (forward) or to the overlap-added gradient (backward): HBM traffic = the two signals, read once (forward)
 // or read + their two gradients (backward).
 //
-//   * one complex n-point transform per frame PAIR: z = w (x + i y); X_k = (Z_k + conj Z_{n-k}) / 2,
-//     Y_k = (Z_k - conj Z_{n-k}) / 2i.  Stockham autosort, radix 8 (+ one radix 2 / 4 pass), n / 8 threads per transform
-//     holding 8 points each, 256 / (n / 8) transforms per workgroup side by side; LDS image padded by one slot per 8 so
-//     that the stride-8 stores of the first pass are conflict free; twiddles from a host-made table (f64 -> f32).
-//   * the two signals of a pair are EQUALISED first (round 5): y enters as s y with s = 2^(exponent of max |x| over the frame -
-//     exponent of max |y|), exact in floating point, and Y = Y' / s after the transform.  A transform's rounding error is
-//     ~ 1e-7 of the norm of its WHOLE input, so without this the quieter signal inherits the louder one's noise: at the start
-//     of training the decoder's output is ~ 50x below the target and d log(|Y| + 1e-7) turned that noise into a multiband
-//     gradient 60 % off the f64 value, where torch's separate f32 transforms are 0.3 % off
-//     (profiles/round5_stft_pair_equalisation.txt).  In the backward the gradient operand is scaled the other way
-//     (Wy / s, result x s), for the same reason: |Wy| ~ s |Wx|.
+//   * one complex n-point transform per frame PAIR of x and y, equalised by a power of two (fft_lds.inc has the transform, the
+//     pair scheme and the equaliser).  In the backward the gradient operand is scaled the other way (Wy / s, result x s), for
+//     the equaliser's own reason: |Wy| ~ s |Wx|.
 //   * backward: the same transform again (the spectra are not stored), the gradient w.r.t. both magnitudes turned into
 //     the Hermitian-extended operand W = Wx + i Wy in place, the unnormalised inverse as swap(FFT(swap(W))) -> real part
 //     = d frame_x, imaginary part = d frame_y, window, overlap-add into an LDS image of the workgroup's span of the padded
@@ -114,9 +106,9 @@ __global__ __launch_bounds__(256) void stft_loss_fwd_kernel(const StftP p) {
     const float eps = p.eps;
     float sc = 1.f, isc = 1.f;       // equaliser of the current frame pair and its inverse (frame_scale)
     auto bin = [&](c32 z1, c32 z2) {
-        const float xr_ = 0.5f * (z1.x + z2.x), xi = 0.5f * (z1.y - z2.y);
-        const float yr_ = (0.5f * isc) * (z1.y + z2.y), yi = (0.5f * isc) * (z2.x - z1.x);
-        const float a2 = xr_ * xr_ + xi * xi, b2 = yr_ * yr_ + yi * yi;
+        c32 X, Y;
+        pair_split(z1, z2, 0.5f, 0.5f * isc, X, Y);
+        const float a2 = X.x * X.x + X.y * X.y, b2 = Y.x * Y.x + Y.y * Y.y;
         const float a = __builtin_amdgcn_sqrtf(a2), b = __builtin_amdgcn_sqrtf(b2);
         const float d = a - b;
         s0 += d * d;
@@ -243,8 +235,8 @@ __global__ __launch_bounds__(256, stft_bwd_occ(N)) void stft_loss_bwd_kernel(con
     // (|Wy| ~ s |Wx| otherwise) and the imaginary part of the inverse transform is multiplied by s where it is added up.
     float sc = 1.f, isc = 1.f;
     auto grads = [&](c32 z1, c32 z2, float gh, c32& gx, c32& gy) {
-        const c32 X = mk(0.5f * (z1.x + z2.x), 0.5f * (z1.y - z2.y));
-        const c32 Y = mk((0.5f * isc) * (z1.y + z2.y), (0.5f * isc) * (z2.x - z1.x));
+        c32 X, Y;
+        pair_split(z1, z2, 0.5f, 0.5f * isc, X, Y);
         const float a = __builtin_amdgcn_sqrtf(X.x * X.x + X.y * X.y), b = __builtin_amdgcn_sqrtf(Y.x * Y.x + Y.y * Y.y);
         const float d = a - b;
         const float sg = d > 0.f ? invN : (d < 0.f ? -invN : 0.f);
@@ -355,7 +347,7 @@ int equalise_on() {       // (read per call: the tests compare both settings in 
 }
 
 bool shape_ok(int n_fft, int hop, int t_len, long rows) {
-    return (n_fft == 128 || n_fft == 256 || n_fft == 512 || n_fft == 1024 || n_fft == 2048) && hop * 4 == n_fft &&
+    return fft_size_ok(n_fft, 2048) && hop * 4 == n_fft &&
            t_len > n_fft / 2 && (long)t_len + 2l * n_fft < 0x7fffffffl && rows > 0 && rows < 65536;
 }
 
@@ -484,14 +476,7 @@ extern "C" int rh_stft_loss_fwd_f32(const float* x, const float* y, const float*
     p.equalise = equalise_on();
     p.part = static_cast<float*>(workspace);
     const int wx = (p.n_frames + p.fpw - 1) / p.fpw;
-    int rc;
-    switch (n_fft) {
-        case 128: rc = launch_fwd<128>(p, wx, (hipStream_t)stream); break;
-        case 256: rc = launch_fwd<256>(p, wx, (hipStream_t)stream); break;
-        case 512: rc = launch_fwd<512>(p, wx, (hipStream_t)stream); break;
-        case 1024: rc = launch_fwd<1024>(p, wx, (hipStream_t)stream); break;
-        default: rc = launch_fwd<2048>(p, wx, (hipStream_t)stream); break;
-    }
+    const int rc = fft_dispatch<2048>(n_fft, [&](auto n) { return launch_fwd<decltype(n)::value>(p, wx, (hipStream_t)stream); });
     if (rc || !sums) return rc;         // sums == NULL: the partials stay in `workspace` for rh_stft_loss_finalize_all_f32
     hipLaunchKernelGGL(stft_loss_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)workspace,
                        (int)(rows * wx), sums);
@@ -530,11 +515,5 @@ extern "C" int rh_stft_loss_bwd_f32(const float* x, const float* y, const float*
     p.inv_n = (float)(1.0 / ((double)rows * p.n_frames * (n_fft / 2 + 1)));
     p.dx = dx; p.dy = dy; p.accumulate = accumulate;
     p.equalise = equalise_on();
-    switch (n_fft) {
-        case 128: return launch_bwd<128>(p, (hipStream_t)stream);
-        case 256: return launch_bwd<256>(p, (hipStream_t)stream);
-        case 512: return launch_bwd<512>(p, (hipStream_t)stream);
-        case 1024: return launch_bwd<1024>(p, (hipStream_t)stream);
-        default: return launch_bwd<2048>(p, (hipStream_t)stream);
-    }
+    return fft_dispatch<2048>(n_fft, [&](auto n) { return launch_bwd<decltype(n)::value>(p, (hipStream_t)stream); });
 }

@@ -1315,7 +1315,7 @@ def _twiddle(n: int, dev) -> Tensor:
     t = _TWIDDLE.get(k)
     if t is None:
         if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("rave_amd multiscale_stft_distance: first call inside a hipGraph capture (run one eager step first)")
+            raise RuntimeError("rave_amd FFT twiddle table: first call inside a hipGraph capture (run one eager step first)")
         import math
         a = torch.arange(n, dtype=torch.float64) * (-2.0 * math.pi / n)
         t = _TWIDDLE[k] = torch.stack([torch.cos(a), torch.sin(a)], -1).to(torch.float32).to(dev).contiguous()
