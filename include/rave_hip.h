@@ -635,6 +635,35 @@ int rh_mel_fwd_f32(const float* x, const float* window, const float* twiddle, co
                    int64_t rows, int32_t t_len, int32_t n_fft, int32_t hop, int32_t n_mels, int32_t n_frames, float scale,
                    int32_t log1p, float* y, rh_stream_t stream);
 
+/* The mel spectrogram WITH its gradient with respect to the audio: the spectrum of the Encodec-style loss,
+ * core.SpectralDistance(mel = n) (rave/core.py:458-468: torchaudio.transforms.MelSpectrogram(sr, n_fft, hop_length = n_fft / 4,
+ * n_mels, power, normalized, center=False), applied to both signals at rave/core.py:484-485), one launch per direction.
+ * x, window, twiddle, fb and bins as for rh_mel_fwd_f32; center = 1: frames centred on f * hop of the reflect-padded row,
+ * frames = t_len / hop + 1; center = 0: frame f is x[f hop, f hop + n_fft), frames = (t_len - n_fft) / hop + 1.
+ *   mel[row][m][f] = sum_k fb[k][m] * |scale * rfft(window * frame_f)_k|^power,   power 1 or 2,
+ * scale = 1 / sqrt(sum(window^2)) for `normalized=True`, else 1 (NOT its square: rh_mel_fwd_f32 takes 1 / sum(window^2)).
+ * rh_mel_diff_fwd_f32 (replaces torchaudio's MelSpectrogram.forward at rave/core.py:484-485) is rh_mel_fwd_f32's kernel with
+ * these two switches; rh_mel_diff_bwd_f32 (replaces autograd through torch.stft, abs / pow and the filterbank product at the
+ * same site) gives dx (rows, t_len) from dmel (laid out as mel) and x: a workgroup owns a span of dx, recomputes the spectrum S
+ * of every frame that covers it, forms dP[k] = sum_m fb[k][m] dmel[m] over the filters whose bin range holds k, the
+ * spectrum's cotangent 2 scale^2 S dP (power 2) or scale S / |S| dP (power 1; exactly 0 where |S| = 0, torch's abs at 0: a
+ * silent row gives zeros, never NaN), the transposed real DFT, the window and the overlap-add with the reflected edges folded
+ * back.  No workspace, no atomics, one writer and one fixed order of additions per sample: bit-identical from run to run;
+ * samples that no frame covers (the uncentred tail) get 0.  Frames ride the transforms two by two, always two of the SAME row.
+ * Sizes (rh_mel_diff_supported answers 1 / 0; a host function): n_fft a power of two in 128 .. 2048, 1 <= hop <= n_fft,
+ * 1 <= n_mels <= 128, power in {1, 2}, center in {0, 1}, t_len >= n_fft (center = 0) or t_len > n_fft / 2 (center = 1),
+ * t_len <= 2^30, 0 < rows < 65536 -- anything else is RH_ERR_UNSUPPORTED; null pointers, a misaligned twiddle table and a
+ * scale that is not positive and finite are RH_ERR_INVALID; nothing is enqueued in any of these cases.  x, mel, dmel and dx
+ * need only be 4-byte aligned. */
+int rh_mel_diff_supported(int32_t n_fft, int32_t hop, int32_t n_mels, int32_t t_len, int64_t rows, int32_t center,
+                          int32_t power);
+int rh_mel_diff_fwd_f32(const float* x, const float* window, const float* twiddle, const float* fb, const int32_t* bins,
+                        int64_t rows, int32_t t_len, int32_t n_fft, int32_t hop, int32_t n_mels, int32_t center, int32_t power,
+                        float scale, float* mel, rh_stream_t stream);
+int rh_mel_diff_bwd_f32(const float* dmel, const float* x, const float* window, const float* twiddle, const float* fb,
+                        const int32_t* bins, int64_t rows, int32_t t_len, int32_t n_fft, int32_t hop, int32_t n_mels,
+                        int32_t center, int32_t power, float scale, float* dx, rh_stream_t stream);
+
 /* The complex spectrogram in front of the spectral discriminators, with its gradient:
  * torchaudio.transforms.Spectrogram(n_fft, hop_length, power=None, normalized, center) followed by
  * cat([s.real, s.imag], 1) (rave/discriminator.py:12-20,147-152, center = 0; rave/descript_discriminator.py:153-160,

@@ -15,6 +15,9 @@ def __getattr__(name):
     if name == "MelSpectrogram":
         from .mel import MelSpectrogram
         return MelSpectrogram
+    if name == "DifferentiableMelSpectrogram":      # the same with a gradient, for losses.SpectralDistance(mel=n)
+        from .mel import DifferentiableMelSpectrogram
+        return DifferentiableMelSpectrogram
     if name == "Spectrogram":           # torchaudio.transforms.Spectrogram's stand-in (rave_amd/spectrogram.py)
         from .spectrogram import Spectrogram
         return Spectrogram

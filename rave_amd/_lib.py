@@ -189,6 +189,9 @@ def _load() -> C.CDLL:
         "rh_stft_loss_bwd_f32": ([P, P, P, P, I64, I32, I32, F, P, P, P, P, I32, P], C.c_int),
         "rh_mel_supported": ([I32, I32, I32, I32, I64], C.c_int),
         "rh_mel_fwd_f32": ([P, P, P, P, P, I64, I32, I32, I32, I32, I32, F, I32, P, P], C.c_int),
+        "rh_mel_diff_supported": ([I32, I32, I32, I32, I64, I32, I32], C.c_int),
+        "rh_mel_diff_fwd_f32": ([P, P, P, P, P, I64, I32, I32, I32, I32, I32, I32, F, P, P], C.c_int),
+        "rh_mel_diff_bwd_f32": ([P, P, P, P, P, P, I64, I32, I32, I32, I32, I32, I32, F, P, P], C.c_int),
         "rh_spectrogram_supported": ([I32, I32, I32, I64, I32], C.c_int),
         "rh_spectrogram_fwd_f32": ([P, P, P, I64, I32, I32, I32, I32, I32, F, P, P], C.c_int),
         "rh_spectrogram_bwd_f32": ([P, P, P, I64, I32, I32, I32, I32, I32, F, P, P], C.c_int),

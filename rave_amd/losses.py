@@ -95,21 +95,37 @@ class WaveformDistance(nn.Module):
 
 
 class SpectralDistance(nn.Module):
-    """rave/core.py:443-490: torchaudio Spectrogram(n_fft, hop = n_fft / 4, power, normalized, center=False) of both signals,
-    then ``mean_difference(y, x, norm)`` summed over the norms.  Beside the hot path and unused by the shipped configs: framing
-    is a strided view, the transform rocFFT (torch.fft), the reductions ATen -- library code on whatever device the signals
-    live on; nothing here is a HIP kernel of this package.  ``mel`` (torchaudio MelSpectrogram, hybrid.gin) is not built."""
+    """rave/core.py:446-490: the spectrum of both signals, then ``mean_difference(y, x, norm)`` summed over the norms.  Unused by
+    the shipped configs (v1 ... v3, discrete use AudioDistanceV1); the Encodec-style loss binds it by gin
+    (rave_amd/configs/mi355x_encodec_mel.gin).
+
+    Without ``mel``: torchaudio Spectrogram(n_fft, hop = n_fft / 4, power, normalized, center=False).  Framing is a strided view,
+    the transform rocFFT (torch.fft), the reductions ATen -- library code on whatever device the signals live on; nothing on
+    this path is a HIP kernel of this package.
+
+    ``mel=n``: torchaudio MelSpectrogram(sampling_rate, n_fft, hop = n_fft / 4, n_mels=n, power, normalized, center=False) as
+    ``rave_amd.mel.DifferentiableMelSpectrogram`` (submodule ``mel_spec``, with torchaudio's two buffers): on GPU float32 signals
+    one HIP launch forward and one backward per signal (rave_amd/csrc/mel.hip), the torch composition elsewhere.  The
+    reductions stay ATen on the small mel tensors.  ``power`` must be 1 or 2 (torchaudio has no complex mel spectrogram)."""
 
     def __init__(self, n_fft: int, sampling_rate: int, norm, power, normalized: bool, mel=None) -> None:
         super().__init__()
-        if mel:
-            raise NotImplementedError("rave_amd SpectralDistance: the mel variant (torchaudio MelSpectrogram) is not built")
         self.n_fft, self.hop, self.power, self.normalized = int(n_fft), int(n_fft) // 4, power, bool(normalized)
-        self.register_buffer("window", torch.hann_window(self.n_fft), persistent=False)
+        if mel:
+            if power is None:
+                raise ValueError("rave_amd SpectralDistance: mel needs power 1 or 2, got power=None (a mel spectrogram of a "
+                                 "complex spectrum is not defined; torchaudio refuses it as well)")
+            from .mel import DifferentiableMelSpectrogram
+            self.mel_spec = DifferentiableMelSpectrogram(int(sampling_rate), self.n_fft, hop_length=self.hop, n_mels=int(mel),
+                                                         power=power, normalized=self.normalized, center=False, pad_mode=None)
+        else:
+            self.register_buffer("window", torch.hann_window(self.n_fft), persistent=False)
         self.norm = (norm,) if isinstance(norm, str) else tuple(norm)
 
     def spec(self, x: torch.Tensor) -> torch.Tensor:
-        """(..., T) -> (..., n_fft / 2 + 1, frames), torch.stft(center=False) layout."""
+        """(..., T) -> (..., n_fft / 2 + 1, frames), torch.stft(center=False) layout; with ``mel``: (..., n_mels, frames)."""
+        if "mel_spec" in self._modules:                                 # (the plain variant has no such attribute at all)
+            return self.mel_spec(x)
         w = self.window.to(x.dtype)
         fr = x.unfold(-1, self.n_fft, self.hop) * w                     # (..., frames, n_fft): no padding (center=False)
         s = torch.fft.rfft(fr, dim=-1).transpose(-1, -2)

@@ -1371,6 +1371,73 @@ def mel_spectrogram(x: Tensor, window: Tensor, fb: Tensor, bins: Tensor, hop: in
     return y
 
 
+# --------------------------------------------------------------------------- differentiable mel spectrogram (Encodec-style loss)
+def mel_diff_supported(n_fft: int, hop: int, n_mels: int, t: int, rows: int, center: bool, power) -> bool:
+    if power not in (1, 2):
+        return False
+    return L.lib.rh_mel_diff_supported(int(n_fft), int(hop), int(n_mels), int(t), int(rows), int(bool(center)), int(power)) == 1
+
+
+def mel_diff_compose(x: Tensor, window: Tensor, fb: Tensor, n_fft: int, hop: int, scale: float, power, center: bool) -> Tensor:
+    """The torch composition (torch.stft, |.|^power, the filterbank product): what CPU tensors, other dtypes and unbuilt sizes
+    take, and what tools/bench_mel_distance.py times against the kernels."""
+    window, fb = window.to(x.dtype), fb.to(x.dtype)
+    shape = x.shape
+    s = torch.stft(x.reshape(-1, shape[-1]), n_fft, hop_length=hop, win_length=n_fft, window=window, center=center,
+                   pad_mode="reflect", normalized=False, onesided=True, return_complex=True)
+    if scale != 1.0:
+        s = s * scale
+    p = s.abs() if power == 1 else s.abs().pow(power)
+    mel = torch.matmul(p.transpose(-1, -2), fb).transpose(-1, -2)
+    return mel.reshape(shape[:-1] + mel.shape[-2:])
+
+
+class _MelDiffFn(torch.autograd.Function):
+    """rh_mel_diff_fwd_f32 / rh_mel_diff_bwd_f32.  The backward recomputes the spectrum: x is saved, not the spectrum."""
+
+    @staticmethod
+    def forward(ctx, x, window, fb, bins, n_fft: int, hop: int, scale: float, power: int, center: bool):
+        x = _chk(x, "x"); window = _chk(window, "window"); fb = _chk(fb, "fb")
+        t, n_mels = x.shape[-1], fb.shape[1]
+        rows = x.numel() // max(t, 1)
+        frames = t // hop + 1 if center else (t - n_fft) // hop + 1
+        mel = torch.empty(x.shape[:-1] + (n_mels, frames), device=x.device, dtype=torch.float32)
+        L.check(L.lib.rh_mel_diff_fwd_f32(L.ptr(x), L.ptr(window), L.ptr(_twiddle(n_fft, x.device)), L.ptr(fb), L.ptr(bins), rows, t,
+                                          n_fft, hop, n_mels, int(center), power, scale, L.ptr(mel), L.stream()), "mel_diff_fwd")
+        ctx.save_for_backward(x, window, fb, bins)
+        ctx.geom = (rows, n_fft, hop, scale, power, center)
+        return mel
+
+    @staticmethod
+    def backward(ctx, dmel):
+        x, window, fb, bins = ctx.saved_tensors
+        rows, n_fft, hop, scale, power, center = ctx.geom
+        dmel = _chk(dmel, "dmel")
+        dx = torch.empty_like(x)
+        L.check(L.lib.rh_mel_diff_bwd_f32(L.ptr(dmel), L.ptr(x), L.ptr(window), L.ptr(_twiddle(n_fft, x.device)), L.ptr(fb),
+                                          L.ptr(bins), rows, x.shape[-1], n_fft, hop, fb.shape[1], int(center), power, scale,
+                                          L.ptr(dx), L.stream()), "mel_diff_bwd")
+        return dx, None, None, None, None, None, None, None, None
+
+
+def mel_spectrogram_diff(x: Tensor, window: Tensor, fb: Tensor, bins: Optional[Tensor], n_fft: int, hop: int, scale: float, power,
+                         center: bool) -> Tensor:
+    """torchaudio.transforms.MelSpectrogram(n_fft, hop_length=hop, power, normalized, center) of x (..., T), differentiable in x:
+    (..., n_mels, frames).  ``scale``: 1 / sqrt(sum(window^2)) for ``normalized=True`` (spectrogram_scale), else 1.0;
+    ``bins`` (n_mels, 2) int32 on x's device: the range of non-zero bins of every filter of ``fb``.  GPU f32 tensors of a built
+    size (rh_mel_diff_supported) run rave_amd/csrc/mel.hip in both directions; CPU tensors, other dtypes and every other size
+    take the torch composition (``bins`` may then be None)."""
+    n_fft, hop, center = int(n_fft), int(hop), bool(center)
+    t = x.shape[-1]
+    rows = x.numel() // max(t, 1)
+    if not (x.is_cuda and x.dtype == torch.float32 and window.numel() == n_fft and tuple(fb.shape[:1]) == (n_fft // 2 + 1,)
+            and mel_diff_supported(n_fft, hop, fb.shape[1], t, rows, center, power)):
+        return mel_diff_compose(x, window, fb, n_fft, hop, float(scale), power, center)
+    if bins is None or bins.dtype != torch.int32 or not bins.is_cuda or not bins.is_contiguous() or tuple(bins.shape) != (fb.shape[1], 2):
+        raise RuntimeError("rave_amd mel_spectrogram_diff: bins must be a contiguous int32 GPU tensor (n_mels, 2)")
+    return _MelDiffFn.apply(x, window, fb, bins, n_fft, hop, float(scale), int(power), center)
+
+
 # --------------------------------------------------------------------------- complex spectrogram (discriminator front ends)
 def spectrogram_supported(n_fft: int, hop: int, t: int, rows: int, center: bool) -> bool:
     return L.lib.rh_spectrogram_supported(int(n_fft), int(hop), int(t), int(rows), int(bool(center))) == 1
