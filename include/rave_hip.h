@@ -834,6 +834,31 @@ int rh_latent_moments_workspace_bytes(int32_t batch, int32_t channels, int32_t t
 int rh_latent_moments_acc_f64(const float* mean, int32_t batch, int32_t channels, int32_t t_len, double* acc, void* workspace,
                               rh_stream_t stream);
 
+/* Filtered-noise synthesis of the noise generators (rave/core.py:48-81 `amp_to_impulse_response` and `fft_convolve` after
+ * `mod_sigmoid`, :23-24, as rave/blocks.py:230-240 `NoiseGenerator.forward` and :282-292 `NoiseGeneratorV2.forward` chain
+ * them), without a transform: both are linear maps of fixed small length.
+ *   amp_j = 2 sigmoid(h - 5)^2.3 + 1e-7,   ir = M amp,   out[b, d, t N + n] = sum_{k <= n} noise[b, t, d, k] ir[n - k]
+ * h (batch, channels * noise_bands, t_len): the last convolution's output, channel d * noise_bands + j (the reference's permute
+ * + reshape); noise (batch, t_len, channels, target_size): the U(-1, 1) draw in the layout of the reference's rand_like(ir);
+ * out (batch, channels, t_len * target_size), written in place of the reference's two permutes.
+ * `table` = M, (target_size, noise_bands) row-major on the device: amp_to_impulse_response applied to the identity (irfft,
+ * roll, Hann window, pad -- or crop, where 2 (noise_bands - 1) > target_size -- roll).  rh_noise_synth_table_f32 fills a HOST
+ * buffer of target_size * noise_bands floats with it, computed in f64 and rounded once.
+ * bwd: gh = d out / d h applied to gout (same layouts; overwritten): d_ir[j] = sum_{n >= j} gout[n] noise[n - j],
+ * d_amp = M^T d_ir, gh = d_amp 4.6 s^2.3 (1 - s) with s = sigmoid(h - 5).  The noise gets no gradient.
+ * One launch each, no workspace, no atomics: every (b, d, t) is computed by one workgroup in a fixed order, so results are
+ * bit-identical from run to run.  Every pointer may be any 4-byte aligned address.
+ * Sizes: 2 <= noise_bands <= 33, 1 <= target_size <= 64 (rh_noise_synth_supported answers 1 / 0), batch, channels,
+ * t_len >= 1 -- other bands / sizes are RH_ERR_UNSUPPORTED; null pointers and non-positive extents RH_ERR_INVALID; nothing is
+ * enqueued in either case. */
+int rh_noise_synth_supported(int32_t noise_bands, int32_t target_size);
+int rh_noise_synth_table_f32(int32_t noise_bands, int32_t target_size, float* table_host);
+int rh_noise_synth_fwd_f32(const float* h, const float* noise, const float* table, int32_t batch, int32_t channels,
+                           int32_t t_len, int32_t noise_bands, int32_t target_size, float* out, rh_stream_t stream);
+int rh_noise_synth_bwd_f32(const float* h, const float* noise, const float* table, const float* gout, int32_t batch,
+                           int32_t channels, int32_t t_len, int32_t noise_bands, int32_t target_size, float* gh,
+                           rh_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -202,6 +202,10 @@ def _load() -> C.CDLL:
         "rh_adain_transfer_f32": ([P, I64, I32, P, P, P, P, P, P], C.c_int),
         "rh_avgpool2_fwd_f32": ([P, I64, I32, P, P], C.c_int),
         "rh_avgpool2_bwd_f32": ([P, I64, I32, P, P], C.c_int),
+        "rh_noise_synth_supported": ([I32, I32], C.c_int),
+        "rh_noise_synth_table_f32": ([I32, I32, P], C.c_int),
+        "rh_noise_synth_fwd_f32": ([P, P, P, I32, I32, I32, I32, I32, P, P], C.c_int),
+        "rh_noise_synth_bwd_f32": ([P, P, P, P, I32, I32, I32, I32, I32, P, P], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol

@@ -295,10 +295,40 @@ def fft_convolve(signal, kernel):
     return output[..., output.shape[-1] // 2:]
 
 
+def _noise_synth_on() -> bool:
+    """The noise generators' tail (mod_sigmoid, amp_to_impulse_response, fft_convolve, the permutes) on one HIP launch per
+    direction (csrc/noise_synth.hip) instead of 62 - 69 ATen / rocFFT launches per pass (profiles/noise_synth.txt); ``RH_NOISE_SYNTH=0`` restores the
+    composition, which CPU tensors and unbuilt sizes take anyway."""
+    import os
+    return os.environ.get("RH_NOISE_SYNTH", "1") != "0"
+
+
+def _noise_table(noise_bands: int, target_size: int) -> Optional[torch.Tensor]:
+    """amp_to_impulse_response as a (target_size, noise_bands) matrix for the kernel, None at a size it is not built for."""
+    if not ops.noise_synth_supported(noise_bands, target_size):
+        return None
+    return ops.noise_synth_table(noise_bands, target_size)
+
+
+def _takes_noise_synth(h, table, noise) -> bool:
+    on_gpu = h.is_cuda and h.dtype == torch.float32 and (noise is None or (noise.is_cuda and noise.dtype == torch.float32))
+    return table is not None and on_gpu and _noise_synth_on()
+
+
+def _noise_synth(h, table, channels: int, noise):
+    """h (B, channels * noise_bands, T), the last convolution's output, to (B, channels, T * target_size).  The draw has the
+    shape, the type and the place in the forward pass of the composition's ``rand_like(ir)``: one seed, one noise."""
+    n, nb = table.shape
+    if noise is None:
+        noise = torch.rand(h.shape[0], h.shape[2], channels, n, dtype=h.dtype, device=h.device) * 2 - 1
+    return ops.noise_synth(h, noise, table, nb, n)
+
+
 class NoiseGeneratorV2(nn.Module):
     """rave/blocks.py:243-292 (configs/v2_small.gin:42-46).  The three strided convolutions
     (kernel 2r, stride r, pad (r,0), no weight norm) run on the HIP kernels with the LeakyReLU between
-    them fused; the filtered-noise synthesis (irfft / rfft) is FFT work on stock torch + rocFFT."""
+    them fused; the filtered-noise synthesis runs on csrc/noise_synth.hip (GPU f32, built sizes) or as the
+    reference's composition (irfft / rfft on stock torch)."""
 
     def __init__(self, in_size: int, hidden_size: int, data_size: int, ratios, noise_bands: int,
                  n_channels: int = 1, activation: Callable[[int], nn.Module] = lambda dim: nn.LeakyReLU(.2)):
@@ -315,6 +345,7 @@ class NoiseGeneratorV2(nn.Module):
         self.net = nn.Sequential(*net)
         self.data_size = data_size
         self.register_buffer("target_size", torch.tensor(int(np.prod(ratios))).long())
+        self.register_buffer("noise_table", _noise_table(noise_bands, int(np.prod(ratios))), persistent=False)
 
     def forward(self, x, act: int = ACT_NONE, slope: float = 0.2, noise: Optional[torch.Tensor] = None):
         """``act``: activation of the CALLER fused into the first conv; ``noise`` injects the
@@ -322,6 +353,8 @@ class NoiseGeneratorV2(nn.Module):
         mods = list(self.net)
         h = mods[0](x, act=act, slope=slope)
         h = run_fused(nn.Sequential(*mods[1:]), h) if len(mods) > 1 else h
+        if _takes_noise_synth(h, self.noise_table, noise):
+            return _noise_synth(h, self.noise_table, self.n_channels * self.data_size, noise)
         amp = mod_sigmoid(h - 5)
         amp = amp.permute(0, 2, 1)
         amp = amp.reshape(amp.shape[0], amp.shape[1], self.n_channels * self.data_size, -1)
@@ -712,7 +745,7 @@ class UpsampleLayer(nn.Module):
 
 
 class NoiseGenerator(nn.Module):
-    """rave/blocks.py:198-240 (v1; configs/v1.gin:71-73: ratios [4,4,4], noise_bands 5)."""
+    """rave/blocks.py:198-240 (v1; configs/v1.gin:71-73: ratios [4,4,4], noise_bands 5).  Synthesis as in NoiseGeneratorV2."""
 
     def __init__(self, in_size, data_size, ratios=(4, 4, 4), noise_bands=5):
         super().__init__()
@@ -726,9 +759,13 @@ class NoiseGenerator(nn.Module):
         self.data_size = data_size
         self.cumulative_delay = 0
         self.register_buffer("target_size", torch.tensor(int(np.prod(ratios))).long())
+        self.register_buffer("noise_table", _noise_table(noise_bands, int(np.prod(ratios))), persistent=False)
 
     def forward(self, x, noise: Optional[torch.Tensor] = None):
-        amp = mod_sigmoid(run_fused(self.net, x) - 5)
+        h = run_fused(self.net, x)
+        if _takes_noise_synth(h, self.noise_table, noise):
+            return _noise_synth(h, self.noise_table, self.data_size, noise)
+        amp = mod_sigmoid(h - 5)
         amp = amp.permute(0, 2, 1)
         amp = amp.reshape(amp.shape[0], amp.shape[1], self.data_size, -1)
         ir = amp_to_impulse_response(amp, self.target_size)

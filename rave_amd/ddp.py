@@ -210,11 +210,12 @@ class BufferSync:
     point-to-point, one large broadcast beats hundreds of small ones); integer buffers (``receptive_field``,
     BatchNorm's ``num_batches_tracked``) are broadcast one by one."""
 
-    # Buffers that no training step writes: filter-bank coefficients, STFT windows, and AdaIN's statistics (the module is
-    # the identity in training mode, rave/blocks.py:901-902; its buffers only move in eval mode).  They are identical on every
+    # Buffers that no training step writes: filter-bank coefficients, STFT windows, the noise generators' synthesis table
+    # (their own float buffer; `target_size` is an integer and travels), and AdaIN's statistics (the module is the identity in training mode, rave/blocks.py:901-902; its buffers only move in eval mode).  They are identical on every
     # rank after broadcast_module() and stay so: not re-sent every step (round 4 broadcast all of them: 1.5 MB of PQMF /
     # window constants and 22 x 4 AdaIN tensors per v3 step).
-    STATIC_OWNERS = ("CachedPQMF", "PQMF", "MultiScaleSTFT", "AdaptiveInstanceNormalization", "Spectrogram", "_Stft")
+    STATIC_OWNERS = ("CachedPQMF", "PQMF", "MultiScaleSTFT", "AdaptiveInstanceNormalization", "Spectrogram", "_Stft",
+                     "NoiseGenerator", "NoiseGeneratorV2")
 
     def __init__(self, module: torch.nn.Module, src: int = 0, process_group=None, force: bool = False,
                  all_buffers: bool = False):

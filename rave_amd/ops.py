@@ -1518,6 +1518,56 @@ def spectrogram(x: Tensor, window: Tensor, n_fft: int, hop: int, normalized: boo
     return _SpectrogramFn.apply(x, window, n_fft, hop, scale, center, bool(cat_channels))
 
 
+# --------------------------------------------------------------------------- filtered-noise synthesis (noise generators)
+def noise_synth_supported(noise_bands: int, target_size: int) -> bool:
+    return L.lib.rh_noise_synth_supported(int(noise_bands), int(target_size)) == 1
+
+
+def noise_synth_table(noise_bands: int, target_size: int) -> Tensor:
+    """amp_to_impulse_response as its (target_size, noise_bands) matrix (rh_noise_synth_table_f32: f64 on the host, rounded
+    once), a CPU tensor."""
+    table = torch.empty(int(target_size), int(noise_bands), dtype=torch.float32)
+    L.check(L.lib.rh_noise_synth_table_f32(int(noise_bands), int(target_size), table.data_ptr()), "noise_synth_table")
+    return table
+
+
+class _NoiseSynthFn(torch.autograd.Function):
+    """rh_noise_synth_fwd_f32 / rh_noise_synth_bwd_f32.  No x6 operands on either side: no range slots."""
+
+    @staticmethod
+    def forward(ctx, h, noise, table, nb: int, n: int):
+        h = _chk(h, "h"); noise = _chk(noise, "noise"); table = _chk(table, "table")
+        b, c, t = h.shape
+        d = c // nb
+        if d * nb != c or tuple(noise.shape) != (b, t, d, n) or tuple(table.shape) != (n, nb):
+            raise RuntimeError(f"rave_amd noise_synth: h {tuple(h.shape)}, noise {tuple(noise.shape)}, table {tuple(table.shape)} "
+                               f"do not fit {nb} noise bands and target size {n}")
+        out = torch.empty(b, d, t * n, device=h.device, dtype=torch.float32)
+        L.check(L.lib.rh_noise_synth_fwd_f32(L.ptr(h), L.ptr(noise), L.ptr(table), b, d, t, nb, n, L.ptr(out), L.stream()),
+                "noise_synth_fwd")
+        ctx.save_for_backward(h, noise, table)
+        ctx.geom = (b, d, t, nb, n)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        h, noise, table = ctx.saved_tensors
+        b, d, t, nb, n = ctx.geom
+        gout = _chk(gout, "gout")
+        gh = torch.empty_like(h)
+        L.check(L.lib.rh_noise_synth_bwd_f32(L.ptr(h), L.ptr(noise), L.ptr(table), L.ptr(gout), b, d, t, nb, n, L.ptr(gh),
+                                             L.stream()), "noise_synth_bwd")
+        return gh, None, None, None, None
+
+
+def noise_synth(h: Tensor, noise: Tensor, table: Tensor, nb: int, N: int) -> Tensor:
+    """The noise generators' tail (rave/blocks.py:230-240, 282-292) from the last convolution's output h (B, D nb, T), before
+    its ``- 5``, and the draw noise (B, T, D, N) to the (B, D, T N) signal: ``mod_sigmoid``, ``amp_to_impulse_response`` as the
+    matrix ``table`` = noise_synth_table(nb, N) on h's device, ``fft_convolve`` as a causal convolution, the permutes as
+    addressing.  Differentiable in h."""
+    return _NoiseSynthFn.apply(h, noise, table, int(nb), int(N))
+
+
 # --------------------------------------------------------------------------- reparametrisation + KL
 class _ReparamFn(torch.autograd.Function):
     """VariationalEncoder.reparametrize (rave/blocks.py:727-745) on rh_reparam_{fwd,bwd}_f32: (zs, kl) from z = [mean | scale]
