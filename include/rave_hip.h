@@ -221,6 +221,23 @@ int rh_amax_f32(const float* x, int64_t n, uint32_t* slot, rh_stream_t stream);
  * (which = 1) would issue; zeros behind `family` for the non-bf16x6 families.  Lets the parity tests assert that the
  * benchmarked batch size runs other template instances than the small-batch tests. */
 int rh_conv1d_plan_info(const rh_conv1d_desc* d, int which, int has_bias, int has_add, int32_t* out8);
+/* Diagnostics (host only, nothing is launched): which INSTANCE of the f32-input MFMA kernels ("family 0") rh_conv1d_fwd_f32
+ * (which = 0) / rh_conv1d_bwd_data_f32 (which = 1) would launch for a call with NO input range slot armed -- answered by the
+ * planning code the launch itself runs.  has_bias / has_add = the optional operands are non-NULL; data_aligned16 = every data
+ * pointer of the call (operands, packed weights, output, workspace) is 16-byte aligned (1) or only 4-byte aligned (0);
+ * workspace_offered = a workspace of rh_conv1d_fwd_workspace_bytes / rh_conv1d_bwd_data_workspace_bytes is passed (1) or none (0).
+ *   out24[0] = family: 0 = f32-input MFMA kernels, 2 = conv_smallc.hip (zeros behind it), 1 = the build's 16-bit kernels take
+ *              the call without a slot (the three-bf16-piece comparison build only; zeros behind it), -1 = empty geometry
+ *   family 0: {0, kernel (1 = conv_igemm_dma_kernel, 0 = conv_igemm_kernel), TM, TN, WM, WN,
+ *              flags (bit 0 LEAKY, bit 1 VEC, bit 2 CTAIL, bit 3 = the DMA launch fell back to conv_igemm_kernel because its two
+ *              stages exceed 160 KiB of LDS), ck, total K chunks, K slices, chunks per slice,
+ *              finalize kernel (0 none, 1 splitk_finalize_kernel, 4 splitk_finalize4_kernel), nb, bnl, tiles_per_b, nphase, inner,
+ *              pitch (floats of one staged row), segs (64-float segments of a staged row, DMA only), LDS bytes,
+ *              grid x, grid y, grid z, the largest number of taps of one phase}
+ * The planner reads RH_CONV_SPLIT_BELOW, RH_CONV_SPLIT_TARGET, RH_CONV_NOVEC and RH_CONV_STAGE_FLOATS once per process.
+ * RH_ERR_UNSUPPORTED where the launch itself would refuse (conv_igemm_kernel's tile beyond 160 KiB of LDS). */
+int rh_conv1d_f32_instance_info(const rh_conv1d_desc* d, int which, int has_bias, int has_add, int data_aligned16,
+                                int workspace_offered, int32_t* out24);
 /* Same question for rh_conv1d_bwd_weight_f32: 1 = wgrad_x6_kernel (bf16 matrix cores; for Conv1d it also produces the
  * bias gradient), 2 = first-layer vector-ALU kernel (weight + bias gradient in one pass), 0 = f32-input MFMA kernels. */
 int rh_conv1d_bwd_weight_kernel_family(const rh_conv1d_desc* d);

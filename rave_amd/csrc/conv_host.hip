@@ -792,6 +792,31 @@ extern "C" int rh_conv1d_plan_info(const rh_conv1d_desc* d, int which, int has_b
     return RH_OK;
 }
 
+// Diagnostics (include/rave_hip.h): the instance of the f32-input MFMA kernels a call WITHOUT an armed input range slot runs.
+// The parameter block is filled as the entry points fill it (pointers stand in for their alignment only) and handed to the
+// planning code of the launches (rh_conv_f32_instance_query); nothing is launched.
+extern "C" int rh_conv1d_f32_instance_info(const rh_conv1d_desc* d, int which, int has_bias, int has_add, int data_aligned16,
+                                           int workspace_offered, int32_t* out24) {
+    RH_REQUIRE(out24, RH_ERR_INVALID, "conv1d_f32_instance_info: null output");
+    RH_REQUIRE(which == 0 || which == 1, RH_ERR_INVALID, "conv1d_f32_instance_info: which must be 0 or 1");
+    for (int i = 0; i < kF32InfoWords; ++i) out24[i] = 0;
+    ConvP p{};
+    if (int e = which == 0 ? rh_conv_fill_fwd(d, &p) : rh_conv_fill_dgrad(d, &p)) return e;
+    if (which == 0 ? rh_smallc_fwd_eligible(d, has_add != 0) : rh_smallc_dgrad_eligible(d, has_add != 0)) { out24[0] = 2; return RH_OK; }
+    // what rh_conv1d_*_workspace_bytes answers for the descriptor (pointers unknown there)
+    const int64_t ws_bytes = workspace_offered ? rh_conv_splitk_workspace(p) : 0;
+    alignas(16) static float dummy[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float* const ptr = dummy + (data_aligned16 ? 0 : 1);
+    p.in = ptr; p.wp = ptr; p.out = ptr;
+    p.wq = reinterpret_cast<const unsigned*>(ptr);
+    p.bias = (which == 0 && has_bias) ? ptr : nullptr;
+    p.add = has_add ? ptr : nullptr;
+    p.mul_src = (which == 1 && d->act != RH_ACT_NONE) ? ptr : nullptr;
+    p.in_alpha = (which == 0 && d->act == RH_ACT_SNAKE) ? ptr : nullptr;
+    p.mul_alpha = (which == 1 && d->act == RH_ACT_SNAKE) ? ptr : nullptr;
+    return rh_conv_f32_instance_query(p, ws_bytes > 0 ? ptr : nullptr, ws_bytes, out24);
+}
+
 extern "C" int rh_conv1d_fwd_f32(const rh_conv1d_desc* d, const float* x, const float* wp_fwd,
                                  const float* bias, const float* snake_alpha, const float* residual,
                                  float* y, void* workspace, int64_t workspace_bytes, rh_stream_t stream) {

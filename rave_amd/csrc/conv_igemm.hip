@@ -164,8 +164,12 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(const ConvP p) 
     }
 }
 
+// What a launch of conv_igemm_kernel<TM, TN, WM, WN> is made of: the tile fields of p, the LDS bytes and the grid.  The launch and
+// rh_conv1d_f32_instance_info both take their answer from here.
+struct CfgPlan { size_t lds; dim3 grid; int maxtaps; };
+
 template <int TM, int TN, int WM, int WN>
-int launch_cfg(ConvP& p, hipStream_t stream, const char* what) {
+CfgPlan plan_cfg(ConvP& p) {
     constexpr int BM = TM * WM * 32, BN = TN * WN * 32;
     // column fold: nb batch items x bnl columns per tile
     int bnl = BN;
@@ -190,10 +194,18 @@ int launch_cfg(ConvP& p, hipStream_t stream, const char* what) {
     const int budget = 15 * 1024;  // floats (60 KiB -> two workgroups per CU)
     const int ck = p.ck = ck_for(budget, (maxtaps > 0 ? maxtaps : 1) * BM + p.nb * p.pitch, p.C, false);
     p.wlds_floats = (maxtaps > 0 ? maxtaps : 1) * ck * BM;
-    const size_t lds = sizeof(float) * ((size_t)p.wlds_floats + (size_t)p.nb * ck * p.pitch);
-    RH_REQUIRE(lds <= 160 * 1024, RH_ERR_UNSUPPORTED, "%s: tile needs %zu B of LDS", what, lds);
-    dim3 grid(rh_cdiv(p.B, p.nb) * p.tiles_per_b, rh_cdiv(p.M, BM), p.nphase);
-    rh_launch_big_lds<conv_igemm_kernel<TM, TN, WM, WN>>(grid, dim3(WM * WN * 64), lds, stream, p);
+    CfgPlan c;
+    c.lds = sizeof(float) * ((size_t)p.wlds_floats + (size_t)p.nb * ck * p.pitch);
+    c.grid = dim3(rh_cdiv(p.B, p.nb) * p.tiles_per_b, rh_cdiv(p.M, BM), p.nphase);
+    c.maxtaps = maxtaps;
+    return c;
+}
+
+template <int TM, int TN, int WM, int WN>
+int launch_cfg(ConvP& p, hipStream_t stream, const char* what) {
+    const CfgPlan c = plan_cfg<TM, TN, WM, WN>(p);
+    RH_REQUIRE(c.lds <= 160 * 1024, RH_ERR_UNSUPPORTED, "%s: tile needs %zu B of LDS", what, c.lds);
+    rh_launch_big_lds<conv_igemm_kernel<TM, TN, WM, WN>>(c.grid, dim3(WM * WN * 64), c.lds, stream, p);
     return rh_check_launch(what);
 }
 
@@ -207,12 +219,32 @@ int rh_conv_launch(ConvP& p, hipStream_t stream, const char* what, void* ws, int
 
 int rh_conv_launch_sync(ConvP& p, hipStream_t stream, const char* what) {
     if (p.B <= 0 || p.ncols <= 0 || p.M <= 0) return RH_OK;
-    int rc;
-    if (p.M <= 32) rc = launch_cfg<1, 2, 1, 4>(p, stream, what);
-    else if (p.M <= 64) rc = launch_cfg<2, 1, 1, 4>(p, stream, what);
-    else if (p.M % 96 == 0 || p.M < 96) rc = launch_cfg<3, 1, 1, 4>(p, stream, what);
-    else rc = launch_cfg<2, 2, 2, 2>(p, stream, what);
+    const int rc = rh_conv_f32_by_shape(p.M, [&](auto s) {
+        using S = decltype(s);
+        return launch_cfg<S::TM, S::TN, S::WM, S::WN>(p, stream, what);
+    });
     return rc ? rc : rh_range_after(p, stream);
+}
+
+int rh_conv_f32_instance_query(ConvP p, void* ws, int64_t ws_bytes, int32_t* out24) {
+    for (int i = 0; i < kF32InfoWords; ++i) out24[i] = 0;
+    if (p.B <= 0 || p.ncols <= 0 || p.M <= 0) { out24[0] = -1; return RH_OK; }       // rh_conv_launch: nothing is launched
+    if (rh_conv_dma_eligible(p)) return rh_conv_dma_instance_query(p, ws, ws_bytes, out24);
+    return rh_conv_sync_instance_query(p, false, out24);
+}
+
+int rh_conv_sync_instance_query(ConvP& p, bool lds_fallback, int32_t* o) {
+    return rh_conv_f32_by_shape(p.M, [&](auto s) -> int {
+        using S = decltype(s);
+        const CfgPlan c = plan_cfg<S::TM, S::TN, S::WM, S::WN>(p);
+        RH_REQUIRE(c.lds <= 160 * 1024, RH_ERR_UNSUPPORTED, "conv1d_f32_instance_info: tile needs %zu B of LDS", c.lds);
+        const int chunks = rh_cdiv(p.C, p.ck);
+        const int32_t v[kF32InfoWords] = {0, 0, S::TM, S::TN, S::WM, S::WN, lds_fallback ? 8 : 0, p.ck, chunks, 1, chunks, 0,
+                                          p.nb, p.bnl, p.tiles_per_b, p.nphase, p.inner, p.pitch, 0, (int32_t)c.lds,
+                                          (int32_t)c.grid.x, (int32_t)c.grid.y, (int32_t)c.grid.z, c.maxtaps};
+        for (int i = 0; i < kF32InfoWords; ++i) o[i] = v[i];
+        return RH_OK;
+    });
 }
 
 // A launch of a kernel family that does not publish the output's range slot (everything but conv_x6_kernel and its finalize

@@ -30,7 +30,10 @@ __device__ __forceinline__ int oidx_of(int n, int inner, int os, int oph) {
     const int r = n / inner;
     return (r * os + oph) * inner + (n - r * inner);
 }
-// n / d for n * d < 2^20 with magic = magic_of(d) = ceil(2^20 / d) (ConvP keeps 20-bit reciprocals: not f32_tile.hpp's mdiv)
+// n / d with magic = magic_of(d) = ceil(2^20 / d) (ConvP keeps 20-bit reciprocals: not f32_tile.hpp's mdiv): EXACT for n * d < 2^20
+// only, never below n / d beyond.  plan_dma keeps every live operand inside: slot g by lpr (it refuses VEC otherwise), rows of
+// at most 8 * 32 and weight rows of at most 64 * 32 + 256 by ck <= 32 (tests/test_f32_matrix_host.py walks all of them).
+// The product is 32 bits wide: n < 2^11 here, magic <= 2^20.
 __device__ __forceinline__ unsigned mdiv20(unsigned n, unsigned magic) { return (n * magic) >> 20; }
 
 template <int TM, int TN, int WM, int WN, bool LEAKY, bool VEC, bool CTAIL>
@@ -390,10 +393,15 @@ __global__ __launch_bounds__(256) void splitk_finalize4_kernel(const ConvP p, lo
     }
 }
 
+// splitk_finalize4_kernel (16-byte accesses) or splitk_finalize_kernel: the launch and rh_conv1d_f32_instance_info both ask here
+bool finalize_vec(const ConvP& p) {
+    return (p.out_valid & 3) == 0 && (p.out_row & 3) == 0 && (p.part_stride & 3) == 0 &&
+           (((uintptr_t)p.part | (uintptr_t)p.out | (uintptr_t)p.mul_src | (uintptr_t)p.add) & 15) == 0;
+}
+
 int finalize_launch(const ConvP& p, hipStream_t stream) {
     const long total = (long)p.B * p.M * p.out_valid;
-    const bool vec = (p.out_valid & 3) == 0 && (p.out_row & 3) == 0 && (p.part_stride & 3) == 0 &&
-                     (((uintptr_t)p.part | (uintptr_t)p.out | (uintptr_t)p.mul_src | (uintptr_t)p.add) & 15) == 0;
+    const bool vec = finalize_vec(p);
     const long items = vec ? total / 4 : total;
     long blocks = rh_cdiv64(items, 256);
     if (p.out_range && blocks > 4096) blocks = 4096;       // one range atomic per workgroup (see the kernels)
@@ -423,10 +431,22 @@ Plan plan_split(const ConvP& p, int BM, int col_tiles) {
     return pl;
 }
 
+// Everything launch_dma<TM, TN, WM, WN> decides before it launches: the tile fields of p, the K split as planned and as taken
+// with the scratch offered, the kernel instance and the grid.  The launch, rh_conv_splitk_workspace and
+// rh_conv1d_f32_instance_info all take their answer from here.
+struct DmaPlan {
+    bool sync_fallback;         // the two stages exceed 160 KiB of LDS: the register-staged kernel runs (p.ksplit / p.part untouched)
+    bool leaky, vec, ctail;     // template arguments of the instance
+    int maxtaps, total_chunks;
+    size_t lds;
+    int64_t need;               // scratch of the split as planned (0 = unsplit); too little offered = the launch runs unsplit
+    dim3 grid;
+};
+
 template <int TM, int TN, int WM, int WN>
-int launch_dma(ConvP& p, hipStream_t stream, const char* what, void* ws, int64_t ws_bytes, bool plan_only = false,
-               int64_t* want = nullptr) {
+DmaPlan plan_dma(ConvP& p, void* ws, int64_t ws_bytes) {
     constexpr int BM = TM * WM * 32, BN = TN * WN * 32;
+    DmaPlan d{};
     int bnl = BN;
     if (p.ncols < BN) {
         bnl = 32;
@@ -470,10 +490,14 @@ int launch_dma(ConvP& p, hipStream_t stream, const char* what, void* ws, int64_t
         const int cmax = (p.C + 1) & ~1;
         if (ck > cmax) ck = cmax;
         if (!vec) break;
-        const int nx = rh_cdiv(p.nb * ck * (p.pitch >> 2), 64 * WM * WN);
+        const int lpr = p.pitch >> 2, xslots = p.nb * ck * lpr;
+        const int nx = rh_cdiv(xslots, 64 * WM * WN);
         const int nws = rh_cdiv(rh_cdiv(maxtaps * ck * BM, 256), WM * WN);
-        if (nx <= 8 && nws <= 10) break;
-        vec = false;   // too many DMA slots per lane: use the element-wise variant
+        // the kernel divides every live slot g < xslots by lpr with mdiv20: exact only while g * lpr < 2^20 (two staged rows of
+        // 724 .. 1024 float4 each were beyond it: the end of the second row was loaded as zeros)
+        const bool exact = (long)(xslots - 1) * lpr < (1l << 20);
+        if (nx <= 8 && nws <= 10 && exact) break;
+        vec = false;   // too many DMA slots per lane, or a slot index the reciprocal cannot divide: use the element-wise variant
     }
     p.ck = ck;
     p.wlds_floats = (maxtaps * ck * BM + 255) & ~255;
@@ -481,34 +505,43 @@ int launch_dma(ConvP& p, hipStream_t stream, const char* what, void* ws, int64_t
     p.magic_segs = magic_of(p.segs);
     p.magic_ck = magic_of(ck);
     p.magic_lpr = magic_of(p.pitch >> 2);
-    const size_t lds = sizeof(float) * 2 * (size_t)p.stage_floats;
+    d.lds = sizeof(float) * 2 * (size_t)p.stage_floats;
     const int col_tiles = rh_cdiv(p.B, p.nb) * p.tiles_per_b;
     Plan pl = plan_split(p, BM, col_tiles);
     p.part_stride = (long)p.B * p.M * p.out_row;
-    const int64_t need = pl.ksplit > 1 ? (int64_t)pl.ksplit * p.part_stride * (int64_t)sizeof(float) : 0;
-    if (plan_only) {
-        *want = lds > 160 * 1024 ? 0 : need;
-        return RH_OK;
-    }
-    if (lds > 160 * 1024) return rh_conv_launch_sync(p, stream, what);
-    if (need > 0 && (!ws || ws_bytes < need)) {   // no scratch offered: run unsplit (slower, same result class)
+    d.need = pl.ksplit > 1 ? (int64_t)pl.ksplit * p.part_stride * (int64_t)sizeof(float) : 0;
+    d.maxtaps = maxtaps;
+    d.total_chunks = pl.total_chunks;
+    d.sync_fallback = d.lds > 160 * 1024;
+    if (d.sync_fallback) return d;
+    if (d.need > 0 && (!ws || ws_bytes < d.need)) {   // no scratch offered: run unsplit (slower, same result class)
         pl.ksplit = 1;
         pl.chunks_per_split = pl.total_chunks;
     }
     p.ksplit = pl.ksplit;
     p.chunks_per_split = pl.chunks_per_split;
     p.part = (float*)ws;
-    const dim3 grid(col_tiles, rh_cdiv(p.M, BM), p.nphase * p.ksplit), block(WM * WN * 64);
-    const bool leaky = p.in_act == RH_ACT_LEAKY;
-    const bool ctail = (p.C % p.ck) != 0;
-    if (vec && !ctail) {
-        if (leaky) rh_launch_big_lds<conv_igemm_dma_kernel<TM, TN, WM, WN, true, true, false>, true>(grid, block, lds, stream, p);
+    d.grid = dim3(col_tiles, rh_cdiv(p.M, BM), p.nphase * p.ksplit);
+    d.leaky = p.in_act == RH_ACT_LEAKY;
+    d.vec = vec;
+    d.ctail = !vec || (p.C % p.ck) != 0;   // (the element-wise variant is instantiated with CTAIL only)
+    return d;
+}
+
+template <int TM, int TN, int WM, int WN>
+int launch_dma(ConvP& p, hipStream_t stream, const char* what, void* ws, int64_t ws_bytes) {
+    const DmaPlan d = plan_dma<TM, TN, WM, WN>(p, ws, ws_bytes);
+    if (d.sync_fallback) return rh_conv_launch_sync(p, stream, what);
+    const dim3 grid = d.grid, block(WM * WN * 64);
+    const size_t lds = d.lds;
+    if (d.vec && !d.ctail) {
+        if (d.leaky) rh_launch_big_lds<conv_igemm_dma_kernel<TM, TN, WM, WN, true, true, false>, true>(grid, block, lds, stream, p);
         else rh_launch_big_lds<conv_igemm_dma_kernel<TM, TN, WM, WN, false, true, false>, true>(grid, block, lds, stream, p);
-    } else if (vec) {
-        if (leaky) rh_launch_big_lds<conv_igemm_dma_kernel<TM, TN, WM, WN, true, true, true>, true>(grid, block, lds, stream, p);
+    } else if (d.vec) {
+        if (d.leaky) rh_launch_big_lds<conv_igemm_dma_kernel<TM, TN, WM, WN, true, true, true>, true>(grid, block, lds, stream, p);
         else rh_launch_big_lds<conv_igemm_dma_kernel<TM, TN, WM, WN, false, true, true>, true>(grid, block, lds, stream, p);
     } else {
-        if (leaky) rh_launch_big_lds<conv_igemm_dma_kernel<TM, TN, WM, WN, true, false, true>, true>(grid, block, lds, stream, p);
+        if (d.leaky) rh_launch_big_lds<conv_igemm_dma_kernel<TM, TN, WM, WN, true, false, true>, true>(grid, block, lds, stream, p);
         else rh_launch_big_lds<conv_igemm_dma_kernel<TM, TN, WM, WN, false, false, true>, true>(grid, block, lds, stream, p);
     }
     if (int e = rh_check_launch(what)) return e;
@@ -549,11 +582,10 @@ int rh_conv_launch_dma(ConvP& p, hipStream_t stream, const char* what, void* ws,
     // f32-input MFMA kernels: they do not publish the output's range; a requested slot is filled by a pass over the output
     unsigned* const orange = p.out_range;
     p.out_range = nullptr;
-    int rc;
-    if (p.M <= 32) rc = launch_dma<1, 2, 1, 4>(p, stream, what, ws, ws_bytes);
-    else if (p.M <= 64) rc = launch_dma<2, 1, 1, 4>(p, stream, what, ws, ws_bytes);
-    else if (p.M % 96 == 0 || p.M < 96) rc = launch_dma<3, 1, 1, 4>(p, stream, what, ws, ws_bytes);
-    else rc = launch_dma<2, 2, 2, 2>(p, stream, what, ws, ws_bytes);
+    const int rc = rh_conv_f32_by_shape(p.M, [&](auto s) {
+        using S = decltype(s);
+        return launch_dma<S::TM, S::TN, S::WM, S::WN>(p, stream, what, ws, ws_bytes);
+    });
     p.out_range = orange;
     return rc ? rc : rh_range_after(p, stream);
 }
@@ -561,11 +593,29 @@ int rh_conv_launch_dma(ConvP& p, hipStream_t stream, const char* what, void* ws,
 int64_t rh_conv_splitk_workspace(ConvP p) {
     if (p.B <= 0 || p.ncols <= 0 || p.M <= 0 || !rh_conv_dma_eligible(p)) return 0;
     fill_sizes(p);
-    int64_t want = 0;
     const int64_t x6 = rh_conv_x6_workspace(p);
-    if (p.M <= 32) launch_dma<1, 2, 1, 4>(p, nullptr, "", nullptr, 0, true, &want);
-    else if (p.M <= 64) launch_dma<2, 1, 1, 4>(p, nullptr, "", nullptr, 0, true, &want);
-    else if (p.M % 96 == 0 || p.M < 96) launch_dma<3, 1, 1, 4>(p, nullptr, "", nullptr, 0, true, &want);
-    else launch_dma<2, 2, 2, 2>(p, nullptr, "", nullptr, 0, true, &want);
+    const int64_t want = rh_conv_f32_by_shape(p.M, [&](auto s) {
+        using S = decltype(s);
+        const DmaPlan d = plan_dma<S::TM, S::TN, S::WM, S::WN>(p, nullptr, 0);
+        return d.sync_fallback ? (int64_t)0 : d.need;
+    });
     return want > x6 ? want : x6;
+}
+
+// mirrors rh_conv_launch_dma
+int rh_conv_dma_instance_query(ConvP& p, void* ws, int64_t ws_bytes, int32_t* o) {
+    fill_sizes(p);
+    if (rh_conv_x6_takes(p)) { o[0] = 1; return RH_OK; }
+    return rh_conv_f32_by_shape(p.M, [&](auto s) -> int {
+        using S = decltype(s);
+        const DmaPlan d = plan_dma<S::TM, S::TN, S::WM, S::WN>(p, ws, ws_bytes);
+        if (d.sync_fallback) return rh_conv_sync_instance_query(p, true, o);
+        const int32_t v[kF32InfoWords] = {0, 1, S::TM, S::TN, S::WM, S::WN, (d.leaky ? 1 : 0) | (d.vec ? 2 : 0) | (d.ctail ? 4 : 0),
+                                          p.ck, d.total_chunks, p.ksplit, p.chunks_per_split,
+                                          p.ksplit > 1 ? (finalize_vec(p) ? 4 : 1) : 0, p.nb, p.bnl, p.tiles_per_b, p.nphase, p.inner,
+                                          p.pitch, p.segs, (int32_t)d.lds,
+                                          (int32_t)d.grid.x, (int32_t)d.grid.y, (int32_t)d.grid.z, d.maxtaps};
+        for (int i = 0; i < kF32InfoWords; ++i) o[i] = v[i];
+        return RH_OK;
+    });
 }

@@ -182,6 +182,24 @@ int rh_conv_launch_sync(ConvP& p, hipStream_t stream, const char* what);   // re
 int rh_range_after(const ConvP& p, hipStream_t stream);                    // fills p.out_range from the output (kernels that do not publish)
 int rh_conv_launch_dma(ConvP& p, hipStream_t stream, const char* what, void* ws, int64_t ws_bytes);
 bool rh_conv_dma_eligible(const ConvP& p);
+// Tile shape <TM, TN, WM, WN> of the f32-input MFMA kernels (32-row / 32-column tiles per wave, waves along rows / columns) for
+// M GEMM rows: f is called with the one F32Shape every launch, scratch query and instance query of conv_igemm*.hip takes.
+template <int TM_, int TN_, int WM_, int WN_>
+struct F32Shape { static constexpr int TM = TM_, TN = TN_, WM = WM_, WN = WN_; };
+template <class F>
+auto rh_conv_f32_by_shape(int M, F&& f) {
+    if (M <= 32) return f(F32Shape<1, 2, 1, 4>{});
+    if (M <= 64) return f(F32Shape<2, 1, 1, 4>{});
+    if (M % 96 == 0 || M < 96) return f(F32Shape<3, 1, 1, 4>{});
+    return f(F32Shape<2, 2, 2, 2>{});
+}
+// rh_conv1d_f32_instance_info (include/rave_hip.h: the 24 numbers): the instance rh_conv_launch would run for p as it stands
+// (pointers for their alignment only, range slots as armed), answered by the planning code of the launches; nothing is launched.
+constexpr int kF32InfoWords = 24;
+int rh_conv_f32_instance_query(ConvP p, void* ws, int64_t ws_bytes, int32_t* out24);
+int rh_conv_dma_instance_query(ConvP& p, void* ws, int64_t ws_bytes, int32_t* out24);
+int rh_conv_sync_instance_query(ConvP& p, bool lds_fallback, int32_t* out24);
+bool rh_conv_x6_takes(ConvP p);                // would rh_conv_launch_x6 / rh_conv_launch_c2x take p as it stands?
 int64_t rh_conv_splitk_workspace(ConvP p);     // bytes of scratch the launch would like (0 = none)
 int64_t rh_conv_x6_workspace(ConvP p);         // bf16x6 path: scratch it needs, -1 = geometry not eligible
 // Which bf16x6 operand layout a geometry gets (decided from the tap plan alone, so that packers and launchers agree):

@@ -295,6 +295,15 @@ bool rh_conv_x6_plan_query(ConvP p, int* out) {
     return true;
 }
 
+// Would rh_conv_launch_x6 / rh_conv_launch_c2x take p as it stands, its input range slot armed or not?  (The two queries above
+// plan with a stand-in slot.)
+bool rh_conv_x6_takes(ConvP p) {
+    if (RH_X6_F16 && !p.in_range) return false;
+    X6Plan pl{};
+    ConvP q = p;
+    return plan_x6(q, &pl) || rh_conv_c2x_query(p);
+}
+
 // Returns RH_OK with *used = false when the geometry (or the scratch offered) does not fit this path.
 int rh_conv_launch_x6(ConvP& p, hipStream_t stream, const char* what, void* ws, int64_t ws_bytes, bool* used) {
     *used = false;

@@ -136,6 +136,9 @@ def _ref_conv(x, w, b, stride, dil, pad, act, slope, alpha, residual):
 
 CONV_CASES = [
     # (B, Cin, Cout, L, k, stride, dil, pad, act, bias, residual)
+    # (one relative L2 over the whole tensor per case; the kernel instances, K modes and tile edges of the f32-input MFMA
+    # kernels these run on without a range slot are pinned and checked slice by slice in tests/f32_matrix.py,
+    # tests/test_f32_matrix_host.py and tests/test_gpu_f32_matrix.py)
     (2, 16, 96, 300, 7, 1, 1, (3, 3), 0, False, False),     # stem
     (2, 96, 96, 257, 3, 1, 9, (9, 9), 1, False, False),     # dilated k3
     (3, 96, 96, 128, 1, 1, 1, (0, 0), 1, False, True),      # pointwise + residual
