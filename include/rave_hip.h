@@ -634,6 +634,41 @@ int rh_stft_loss_bwd_f32(const float* x, const float* y, const float* window, co
                          int32_t t_len, int32_t n_fft, float eps, const float* sums, const float* grad_out, float* dx,
                          float* dy, int32_t accumulate, rh_stream_t stream);
 
+/* WeightedInstantaneousSpectralDistance on one STFT scale (rave/core.py:347-412 over MultiScaleSTFT(magnitude=False),
+ * rave/core.py:269-319: Spectrogram(n_fft, hop = n_fft / 4, center, reflect, power=None) -> abs / log1p / angle -> unwrap ->
+ * derivative -> optional mask -> the two means) with the transform INSIDE the kernel.  x = target, y = prediction, (rows, t_len)
+ * f32, not overlapping any output; window (n_fft: the window the frames are multiplied by, `normalized` folded in); twiddle:
+ * n_fft complex FLOAT64 values e^{-2 pi i k / n_fft}, interleaved, 16-byte aligned (the transform runs in f64: a phase is as
+ * wrong as the transform's error over |bin|).  Supported: n_fft in {128 ... 2048}, hop = n_fft / 4, t_len > n_fft / 2
+ * (rh_inst_freq_loss_supported: the set of rh_stft_loss_supported).  frames = t_len / hop + 1, bins = n_fft / 2 + 1.
+ *   sums[4] = sum (a-b)^2, sum a^2, sum |log1p a - log1p b| over rows x bins x frames (a = |X|, b = |Y|), and
+ *             sum (m IFx - m IFy)^2 over rows x bins x (frames - 2), IF[j] = wrap(phi[j+2] - phi[j+1]) along the FRAMES,
+ *             wrap(d) = ((d + pi) mod 2 pi) - pi in f32 with torch.remainder's sign; m = clip(log1p a[j+2], 0, 1) (weighted != 0:
+ *             the mask comes from the target) or 1.  The reference's cumsum-then-diff cancels and is not computed.
+ *   Sum order: per workgroup (a span of frames of one row, walked in order; one more frame to its left is transformed for its
+ *   phases) a fixed tree; the partials lie in (row, workgroup) order in `workspace` (rh_inst_freq_loss_workspace_bytes) and
+ *   rh_inst_freq_loss_finalize_all_f32 adds them in a fixed order for ALL scales in one launch: sums (n_scales x 4),
+ *   out2[0] = sum_s sums[s][0] / sums[s][1] + sums[s][2] * inv_n[2s] (spectral_distance), out2[1] = sum_s sums[s][3] *
+ *   inv_n[2s+1] (phase_distance); inv_n: DEVICE array, 1 / (rows bins frames) and 1 / (rows bins (frames - 2)) per scale;
+ *   partials[s] / partial_bytes[s]: HOST arrays.  No atomics: the bits are reproducible; every launch can be captured.
+ *   Exact by construction: (1) bins 0 and n_fft / 2 have an imaginary part of exactly +0, phases 0 or pi, and IF exactly 0
+ *   or -pi (wrap maps +pi and -pi to -pi, as the reference's f32 arithmetic); (2) a bin that is exactly zero has phase 0
+ *   (torch.angle), so a silent row has IF = 0 and a zero gradient.
+ *   if_out (diagnostics, may be NULL): (rows, 2, bins, frames - 2) -- the unweighted IF of x and of y.
+ * Backward: recomputes the spectra; grad_out2 = 2 DEVICE scalars (d / d spectral_distance, d / d phase_distance), sums = the
+ * 4 sums of THIS scale; writes (accumulate = 0) or adds (!= 0) dx and dy (either may be NULL).  d angle / d (re, im) =
+ * (-im, re) / |z|^2, 0 at z = 0; wrap has derivative 1; the mask sends a gradient to x where log1p a <= 1. */
+int rh_inst_freq_loss_supported(int32_t n_fft, int32_t hop, int32_t t_len, int64_t rows);
+int64_t rh_inst_freq_loss_workspace_bytes(int32_t n_fft, int32_t t_len, int64_t rows);
+int rh_inst_freq_loss_fwd_f32(const float* x, const float* y, const float* window, const double* twiddle, int64_t rows,
+                              int32_t t_len, int32_t n_fft, int32_t weighted, float* if_out, void* workspace,
+                              int64_t workspace_bytes, rh_stream_t stream);
+int rh_inst_freq_loss_finalize_all_f32(const float* const* partials, const int64_t* partial_bytes, int32_t n_scales,
+                                       const float* inv_n, float* sums, float* out2, rh_stream_t stream);
+int rh_inst_freq_loss_bwd_f32(const float* x, const float* y, const float* window, const double* twiddle, int64_t rows,
+                              int32_t t_len, int32_t n_fft, int32_t weighted, const float* sums, const float* grad_out2,
+                              float* dx, float* dy, int32_t accumulate, rh_stream_t stream);
+
 /* The mel-spectrogram encoder input of RAVE.input_mode = "mel" (rave/model.py:238-242: `spectrogram(x)[..., :-1]`, log1p,
  * reshape; spectrogram = torchaudio.transforms.MelSpectrogram as configs/hybrid.gin binds it) in one launch, forward only
  * (nothing trainable is upstream of the audio).  x (rows, t_len) f32; window (n_fft: the module's `spectrogram.window`);

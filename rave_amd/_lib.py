@@ -203,6 +203,11 @@ def _load() -> C.CDLL:
         "rh_adain_transfer_f32": ([P, I64, I32, P, P, P, P, P, P], C.c_int),
         "rh_avgpool2_fwd_f32": ([P, I64, I32, P, P], C.c_int),
         "rh_avgpool2_bwd_f32": ([P, I64, I32, P, P], C.c_int),
+        "rh_inst_freq_loss_supported": ([I32, I32, I32, I64], C.c_int),
+        "rh_inst_freq_loss_workspace_bytes": ([I32, I32, I64], I64),
+        "rh_inst_freq_loss_fwd_f32": ([P, P, P, P, I64, I32, I32, I32, P, P, I64, P], C.c_int),
+        "rh_inst_freq_loss_finalize_all_f32": ([C.POINTER(C.c_void_p), C.POINTER(I64), I32, P, P, P, P], C.c_int),
+        "rh_inst_freq_loss_bwd_f32": ([P, P, P, P, I64, I32, I32, I32, P, P, P, P, I32, P], C.c_int),
         "rh_noise_synth_supported": ([I32, I32], C.c_int),
         "rh_noise_synth_table_f32": ([I32, I32, P], C.c_int),
         "rh_noise_synth_fwd_f32": ([P, P, P, I32, I32, I32, I32, I32, P, P], C.c_int),

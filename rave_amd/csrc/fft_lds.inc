@@ -1,9 +1,10 @@
-// The frame-pair FFT stage of stft_loss.hip, mel.hip, spectrogram.hip and feed_mask.hip.  Included INSIDE the including file's
+// The frame-pair FFT stage of stft_loss.hip, mel.hip, spectrogram.hip, feed_mask.hip and inst_freq_loss.hip.  Included INSIDE the including file's
 // anonymous namespace, after common.hpp; the device pieces come first, the host's checks and size dispatcher last.
 //
 //   * the transform: an in-LDS complex FFT, N = 128 ... 2048.  Stockham autosort, radix 8 (+ one radix 2 / 4 pass), N / 8 threads per
 //     transform holding 8 points each, 256 / (N / 8) transforms per workgroup side by side; the LDS image is padded by one slot per
 //     8 (zpad) so that the stride-8 stores of the first pass are conflict free; twiddles from a host-made table (f64 -> f32).
+//     Written once for c32 (every unit's default) and c64 (Fft<N, c64> with an f64 table: inst_freq_loss.hip).
 //   * the pair scheme: two real frames ride one transform as z = w (x + i y) and are split by X_k = (Z_k + conj Z_{n-k}) / 2,
 //     Y_k = (Z_k - conj Z_{n-k}) / 2i (pair_split; each kernel walks the bin pairs itself).
 //   * the equaliser (frame_scale, round 5): the two frames of a pair are EQUALISED first, y enters as s y with s = 2^(exponent of
@@ -19,45 +20,53 @@
 
 typedef float c32 __attribute__((ext_vector_type(2)));       // complex as a packed pair: adds / twiddle products are v_pk_* ops
 
+// the same in double: the transform (cmul ... Fft below) is written once for both; inst_freq_loss.hip runs it on c64, every
+// other unit on c32 (the default)
+typedef double c64 __attribute__((ext_vector_type(2)));
+
 __device__ __forceinline__ c32 mk(float a, float b) { c32 r; r.x = a; r.y = b; return r; }
-__device__ __forceinline__ c32 cmul(c32 a, c32 w) {
-    c32 r = a.xx * w;
+__device__ __forceinline__ c64 mk(double a, double b) { c64 r; r.x = a; r.y = b; return r; }
+template <class C>
+__device__ __forceinline__ C cmul(C a, C w) {
+    C r = a.xx * w;
     return __builtin_elementwise_fma(a.yy, mk(-w.y, w.x), r);
 }
-__device__ __forceinline__ c32 mul_mi(c32 a) { return mk(a.y, -a.x); }          // a * (-i)
+template <class C>
+__device__ __forceinline__ C mul_mi(C a) { return mk(a.y, -a.x); }          // a * (-i)
 
 // forward DFTs (e^{-i}) of 2 / 4 / 8 points in natural order, in place on v[0], v[S], v[2S] ...
-template <int S>
-__device__ __forceinline__ void dft2(c32* v) {
-    const c32 a = v[0], b = v[S];
+template <int S, class C>
+__device__ __forceinline__ void dft2(C* v) {
+    const C a = v[0], b = v[S];
     v[0] = a + b;
     v[S] = a - b;
 }
-template <int S>
-__device__ __forceinline__ void dft4(c32* v) {
-    const c32 b0 = v[0] + v[2 * S], b1 = v[0] - v[2 * S];
-    const c32 b2 = v[S] + v[3 * S], b3 = mul_mi(v[S] - v[3 * S]);
+template <int S, class C>
+__device__ __forceinline__ void dft4(C* v) {
+    const C b0 = v[0] + v[2 * S], b1 = v[0] - v[2 * S];
+    const C b2 = v[S] + v[3 * S], b3 = mul_mi(C(v[S] - v[3 * S]));
     v[0] = b0 + b2;
     v[S] = b1 + b3;
     v[2 * S] = b0 - b2;
     v[3 * S] = b1 - b3;
 }
-__device__ __forceinline__ void dft8(c32* v) {
+template <class C>
+__device__ __forceinline__ void dft8(C* v) {
     dft4<2>(v);          // even samples -> E_k at v[2k]
     dft4<2>(v + 1);      // odd samples  -> O_k at v[2k+1]
-    constexpr float kR = 0.70710678118654752440f;
-    const c32 e0 = v[0], e1 = v[2], e2 = v[4], e3 = v[6];
-    const c32 o0 = v[1];
-    const c32 o1 = mk(v[3].x + v[3].y, v[3].y - v[3].x) * kR;         // * (1 - i) / sqrt 2
-    const c32 o2 = mul_mi(v[5]);
-    const c32 o3 = mk(v[7].y - v[7].x, -(v[7].x + v[7].y)) * kR;      // * (-1 - i) / sqrt 2
+    constexpr decltype(C().x) kR = 0.70710678118654752440;
+    const C e0 = v[0], e1 = v[2], e2 = v[4], e3 = v[6];
+    const C o0 = v[1];
+    const C o1 = mk(v[3].x + v[3].y, v[3].y - v[3].x) * kR;         // * (1 - i) / sqrt 2
+    const C o2 = mul_mi(v[5]);
+    const C o3 = mk(v[7].y - v[7].x, -(v[7].x + v[7].y)) * kR;      // * (-1 - i) / sqrt 2
     v[0] = e0 + o0; v[4] = e0 - o0;
     v[1] = e1 + o1; v[5] = e1 - o1;
     v[2] = e2 + o2; v[6] = e2 - o2;
     v[3] = e3 + o3; v[7] = e3 - o3;
 }
-template <int R>
-__device__ __forceinline__ void dft(c32* v) {
+template <int R, class C>
+__device__ __forceinline__ void dft(C* v) {
     if (R == 8) dft8(v);
     else if (R == 4) dft4<1>(v);
     else dft2<1>(v);
@@ -128,7 +137,7 @@ __device__ __forceinline__ void frame_scale(const c32 (&vn)[8], c32* fmx, float&
     inv_s = __uint_as_float((unsigned)(127 - d) << 23);
 }
 
-template <int N>
+template <int N, class C = c32>
 struct Fft {
     static constexpr int TPF = N / 8;                       // threads per transform
     static constexpr int G = 256 / TPF;                     // transforms per workgroup
@@ -149,13 +158,13 @@ struct Fft {
 
     // every twiddle a thread ever needs depends on its index alone: fetched once, kept in registers across the frames
     struct Tw {
-        c32 a[7];            // pass NS = 8
-        c32 b[MID2 ? 7 : 1]; // pass NS = 64 (1024 / 2048 only)
-        c32 f[NTF];          // final pass
+        C a[7];            // pass NS = 8
+        C b[MID2 ? 7 : 1]; // pass NS = 64 (1024 / 2048 only)
+        C f[NTF];          // final pass
         // `tw` holds e^{-2 pi i k / (S N)}, k < S N: S = 1 is the transform's own table, S = 2 the table of a real transform of
         // 2 N points packed into this one (feed_mask.hip), whose even entries are this transform's
         template <int S = 1>
-        __device__ __forceinline__ void init(int t, const c32* __restrict__ tw) {
+        __device__ __forceinline__ void init(int t, const C* __restrict__ tw) {
 #pragma unroll
             for (int r = 1; r < 8; ++r) a[r - 1] = tw[S * r * (t & 7) * (N / 64)];
             if (MID2) {
@@ -176,34 +185,34 @@ struct Fft {
     // per-thread base plus a compile-time constant (n/8 and NS >= 8 are multiples of 8): immediate offsets, no index math
     // per access.
     template <int R>
-    static __device__ __forceinline__ void load(c32 (&v)[8], const c32* z, int t, const c32* w) {
-        const c32* zt = z + zpad(t);
+    static __device__ __forceinline__ void load(C (&v)[8], const C* z, int t, const C* w) {
+        const C* zt = z + zpad(t);
 #pragma unroll
         for (int u = 0; u < 8 / R; ++u) {
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                c32 a = zt[(u * TPF + r * (N / R)) / 8 * 9];
+                C a = zt[(u * TPF + r * (N / R)) / 8 * 9];
                 if (r > 0) a = cmul(a, w[u * (R - 1) + r - 1]);
                 v[u * R + r] = a;
             }
         }
     }
     template <int R>
-    static __device__ __forceinline__ void bfly(c32 (&v)[8]) {
+    static __device__ __forceinline__ void bfly(C (&v)[8]) {
 #pragma unroll
         for (int u = 0; u < 8 / R; ++u) dft<R>(&v[u * R]);
     }
     // radix-8 passes only (R = 8, one butterfly per thread: j = t)
     template <int NS>
-    static __device__ __forceinline__ void store8(const c32 (&v)[8], c32* z, int t) {
+    static __device__ __forceinline__ void store8(const C (&v)[8], C* z, int t) {
         const int k = t & (NS - 1);
         // NS = 1: 9 t + r;  NS = 8: 9 (t - k) + k + 9 r;  NS = 64: 9 (t - k) + k + k / 8 + 72 r
-        c32* zt = z + 9 * (t - k) + k + (k >> 3);
+        C* zt = z + 9 * (t - k) + k + (k >> 3);
 #pragma unroll
         for (int r = 0; r < 8; ++r) zt[NS == 1 ? r : r * NS / 8 * 9] = v[r];
     }
     template <int NS>
-    static __device__ __forceinline__ void pass8(c32 (&v)[8], c32* z, int t, const c32* w) {
+    static __device__ __forceinline__ void pass8(C (&v)[8], C* z, int t, const C* w) {
         load<8>(v, z, t, w);
         bfly<8>(v);
         sync();
@@ -213,7 +222,7 @@ struct Fft {
     // first pass with the 8 inputs v[r] = in[t + r TPF] already in registers; leaves everything but the final pass done
     // and returns with the final pass's butterflies in v: output r of butterfly u is sample (t + u TPF) + r NSF.
     // Every thread of the workgroup must call it (barriers); the caller guarantees nobody still reads z.
-    static __device__ __forceinline__ void run(c32 (&v)[8], c32* z, int t, const Tw& tw) {
+    static __device__ __forceinline__ void run(C (&v)[8], C* z, int t, const Tw& tw) {
         bfly<8>(v);
         store8<1>(v, z, t);
         sync();
@@ -225,8 +234,8 @@ struct Fft {
     }
     static __device__ __forceinline__ int out_index(int t, int u, int r) { return t + u * TPF + r * NSF; }
     // natural-order spectrum into z (barrier at the end)
-    static __device__ __forceinline__ void store_natural(const c32 (&v)[8], c32* z, int t) {
-        c32* zt = z + zpad(t);
+    static __device__ __forceinline__ void store_natural(const C (&v)[8], C* z, int t) {
+        C* zt = z + zpad(t);
 #pragma unroll
         for (int u = 0; u < 8 / RF; ++u)
 #pragma unroll

@@ -38,16 +38,29 @@ def hinge_gan(score_real, score_fake):
 
 
 class MultiScaleSTFT(nn.Module):
-    """rave/core.py:269-319 with magnitude=True, no mel; torchaudio.transforms.Spectrogram(n_fft=s,
-    win_length=s, hop_length=s//4, power=None) == torch.stft(periodic Hann, center, reflect)."""
+    """rave/core.py:269-319 without mel; torchaudio.transforms.Spectrogram(n_fft=s, win_length=s, hop_length=s//4,
+    normalized, power=None) == torch.stft(periodic Hann, center, reflect) [/ sqrt(sum(window^2))].  ``normalized`` is folded
+    into the ``window_<s>`` buffers (the transform is linear in the window), so every consumer of them sees it.
+    ``magnitude=False``: ``forward`` returns the reference's ``stack([re, im], -1)``, (rows, bins, frames, 2) per scale, from
+    the rave_amd.Spectrogram kernel (rave_amd/csrc/spectrogram.hip) where rh_spectrogram_supported holds and from torch.stft
+    elsewhere (CPU tensors, other dtypes, unbuilt sizes)."""
 
-    def __init__(self, scales: Sequence[int], sample_rate: int = 44100, magnitude: bool = True):
+    def __init__(self, scales: Sequence[int], sample_rate: int = 44100, magnitude: bool = True, normalized: bool = False,
+                 num_mels=None):
         super().__init__()
-        if not magnitude:
-            raise NotImplementedError
+        if num_mels is not None:
+            raise NotImplementedError("rave_amd MultiScaleSTFT: num_mels is not built (the mel variant of the spectral losses is "
+                                      "SpectralDistance(mel=...), rave_amd/configs/mi355x_encodec_mel.gin)")
         self.scales = list(scales)
+        self.magnitude, self.normalized, self.num_mels = bool(magnitude), bool(normalized), None
         for s in self.scales:
-            self.register_buffer(f"window_{s}", torch.hann_window(s), persistent=False)
+            w = torch.hann_window(s)
+            if self.normalized:
+                w = (w.double() / w.double().pow(2).sum().sqrt()).float()
+            self.register_buffer(f"window_{s}", w, persistent=False)
+
+    def windows(self):
+        return [getattr(self, f"window_{s}") for s in self.scales]
 
     def complex_stfts(self, x):
         """Complex spectrograms (rows, frames, bins): torch.stft's with the (frequency, frame) axes swapped."""
@@ -57,8 +70,13 @@ class MultiScaleSTFT(nn.Module):
         return [torch.fft.rfft(ops.stft_frames(x, getattr(self, f"window_{s}"), s, s // 4), dim=-1) for s in self.scales]
 
     def forward(self, x):
-        """Magnitudes in torch.stft's (rows, bins, frames) layout."""
-        return [y.abs().transpose(-1, -2) for y in self.complex_stfts(x)]
+        """Magnitudes in torch.stft's (rows, bins, frames) layout; with ``magnitude=False`` (rows, bins, frames, 2)."""
+        if self.magnitude:
+            return [y.abs().transpose(-1, -2) for y in self.complex_stfts(x)]
+        from . import ops
+        x = x.reshape(-1, x.shape[-1])
+        # the window buffer carries the normalisation already: normalized=False below
+        return [ops.spectrogram(x, w, s, s // 4, False, True).movedim(-3, -1) for s, w in zip(self.scales, self.windows())]
 
 
 class AudioDistanceV1(nn.Module):
@@ -80,6 +98,35 @@ class AudioDistanceV1(nn.Module):
         distance = ops.multiscale_stft_distance(xr, yr, [getattr(ms, f"window_{s}") for s in ms.scales], ms.scales,
                                                 float(self.log_epsilon))
         return {"spectral_distance": distance}
+
+
+class WeightedInstantaneousSpectralDistance(nn.Module):
+    """rave/core.py:347-412: the amplitude distance with log1p, plus ``phase_distance``, the mean squared difference of the
+    instantaneous frequencies (wrapped phase differences along the frames), optionally weighted by clip(log1p|X|, 0, 1) of the
+    target.  ``multiscale_stft`` must build a ``MultiScaleSTFT(magnitude=False)``.
+
+    f32 GPU signals at built scales run one HIP launch per scale and direction with the transform inside
+    (rave_amd/csrc/inst_freq_loss.hip, ``ops.multiscale_inst_freq_distance``); CPU tensors, other dtypes and unbuilt scales run
+    the reference's torch composition, cumsum included (``ops.inst_freq_compose``), and so does everything under
+    ``RH_INST_FREQ=0``.  Bound by rave_amd/configs/mi355x_phase.gin; no shipped default selects it."""
+
+    def __init__(self, multiscale_stft, weighted: bool = False) -> None:
+        super().__init__()
+        self.multiscale_stft = multiscale_stft()
+        if getattr(self.multiscale_stft, "magnitude", False):
+            raise ValueError("rave_amd WeightedInstantaneousSpectralDistance: needs MultiScaleSTFT(magnitude=False) (the "
+                             "reference asserts a trailing (re, im) axis, rave/core.py:377)")
+        self.weighted = weighted
+
+    def forward(self, target, pred):
+        from . import ops
+        ms = self.multiscale_stft
+        xr, yr = target.reshape(-1, target.shape[-1]), pred.reshape(-1, pred.shape[-1])
+        fused = (xr.is_cuda and yr.is_cuda and xr.dtype == torch.float32 and yr.dtype == torch.float32 and ops.inst_freq_on()
+                 and ops.inst_freq_supported(ms.scales, xr.shape[-1], xr.shape[0]))
+        fn = ops.multiscale_inst_freq_distance if fused else ops.inst_freq_compose
+        spectral_distance, phase_distance = fn(xr, yr, ms.windows(), ms.scales, bool(self.weighted))
+        return {"spectral_distance": spectral_distance, "phase_distance": phase_distance}
 
 
 # ---- the other distances of rave/core.py (:415-490); no shipped config selects them (v1 ... v3, discrete use AudioDistanceV1)

@@ -821,7 +821,7 @@ def build_v2(n_channels: int = 1, capacity: int = 96, ratios=(4, 4, 4, 2), laten
              codebook_size: int = 1024, log_epsilon: float = 1e-7, num_skipped_features: int = 1,
              spectral_capacity: int = 32, gru_layers: int = 0, mel_input: bool = False, n_fft: int = 2048,
              hop_length: int = 256, n_mels: int = 128, encoder_ratios=(2, 2, 2), encoder_dilations=(1,),
-             latent_analysis: bool = False, hip_frontend: bool = False) -> RAVE:
+             latent_analysis: bool = False, hip_frontend: bool = False, phase_distance: bool = False) -> RAVE:
     """configs/v1.gin + configs/v2.gin transcribed (cf. oracle/ref_models.py for the citations).
     ``snake`` / ``adain`` add the generator-side overlays of configs/v3.gin (snake.gin: every activation
     -> blocks.Snake; adain.gin: AdaptiveInstanceNormalization before every unit); ``causal`` =
@@ -835,7 +835,10 @@ def build_v2(n_channels: int = 1, capacity: int = 96, ratios=(4, 4, 4, 2), laten
     ``latent_analysis`` registers the reference's ``latent_pca`` / ``latent_mean`` / ``fidelity`` buffers (rave/model.py:196-198),
     which ``validation_epoch_end`` then fills; off by default, the state_dict keys are then unchanged.
     ``hip_frontend`` hands the complex spectrograms of the "spectral" and "descript" discriminators to
-    rave_amd/csrc/spectrogram.hip (the gin route: rave_amd/configs/mi355x_spectrogram*.gin); off by default."""
+    rave_amd/csrc/spectrogram.hip (the gin route: rave_amd/configs/mi355x_spectrogram*.gin); off by default.
+    ``phase_distance`` binds the fullband distance to losses.WeightedInstantaneousSpectralDistance (weighted, over the
+    normalised complex multi-scale STFT) as rave_amd/configs/mi355x_phase.gin does: the step then logs and trains on
+    ``fullband_phase_distance`` as well; off by default."""
     ratios = list(ratios)
     spectrogram = None
     if mel_input:
@@ -905,12 +908,17 @@ def build_v2(n_channels: int = 1, capacity: int = 96, ratios=(4, 4, 4, 2), laten
     stft = partial(losses.MultiScaleSTFT, scales=[2048, 1024, 512, 256, 128], sample_rate=sampling_rate,
                    magnitude=True)
     dist = partial(losses.AudioDistanceV1, multiscale_stft=stft, log_epsilon=log_epsilon)
+    full_dist = dist
+    if phase_distance:      # rave_amd/configs/mi355x_phase.gin: the fullband distance only, the multiband one stays
+        full_dist = partial(losses.WeightedInstantaneousSpectralDistance, weighted=True,
+                            multiscale_stft=partial(losses.MultiScaleSTFT, scales=[2048, 1024, 512, 256, 128],
+                                                    sample_rate=sampling_rate, magnitude=False, normalized=True))
     model = RAVE(latent_size=latent_size, sampling_rate=sampling_rate,
                  pqmf=partial(pqmf.CachedPQMF, attenuation=100, n_band=n_band),
                  encoder=enc, decoder=dec, discriminator=disc, phase_1_duration=1000000,
                  gan_loss=losses.hinge_gan, valid_signal_crop=True,
                  feature_matching_fun=partial(losses.mean_difference, norm="L1", relative=True),
-                 num_skipped_features=num_skipped_features, audio_distance=dist, multiband_audio_distance=dist,
+                 num_skipped_features=num_skipped_features, audio_distance=full_dist, multiband_audio_distance=dist,
                  weights={"feature_matching": 20}, update_discriminator_every=update_discriminator_every,
                  n_channels=n_channels, n_bands=n_band, spectrogram=spectrogram,
                  input_mode="mel" if mel_input else "pqmf", latent_analysis=latent_analysis)

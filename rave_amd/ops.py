@@ -1322,6 +1322,23 @@ def _twiddle(n: int, dev) -> Tensor:
     return t
 
 
+_TWIDDLE64 = {}
+
+
+def _twiddle64(n: int, dev) -> Tensor:
+    """e^{-2 pi i k / n}, k < n, as (n, 2) f64 (inst_freq_loss.hip transforms in f64), made once per size and device outside any
+    capture."""
+    k = (int(n), str(dev))
+    t = _TWIDDLE64.get(k)
+    if t is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("rave_amd FFT twiddle table: first call inside a hipGraph capture (run one eager step first)")
+        import math
+        a = torch.arange(n, dtype=torch.float64) * (-2.0 * math.pi / n)
+        t = _TWIDDLE64[k] = torch.stack([torch.cos(a), torch.sin(a)], -1).to(dev).contiguous()
+    return t
+
+
 def _stft_fused_ok(scales, t: int, rows: int) -> bool:
     if os.environ.get("RH_STFT_FUSED", "1") == "0":      # 0: framing kernels + rocFFT + spectral kernels (the older path)
         return False
@@ -1340,6 +1357,126 @@ def multiscale_stft_distance(x: Tensor, y: Tensor, windows, scales, eps: float) 
     """sum over the scales of mean((|Sx|-|Sy|)^2)/mean(|Sx|^2) + mean(|log(|Sx|+eps) - log(|Sy|+eps)|) for (rows, T) signals.
 """
     return _MultiScaleStftDistanceFn.apply(x, y, float(eps), tuple(int(s) for s in scales), *windows)
+
+
+# --------------------------------------------------------------------------- instantaneous-frequency (phase) distance
+def inst_freq_supported(scales, t: int, rows: int) -> bool:
+    return all(L.lib.rh_inst_freq_loss_supported(int(n), int(n) // 4, int(t), int(rows)) == 1 for n in scales)
+
+
+def inst_freq_on() -> bool:
+    """``RH_INST_FREQ=0``: the torch composition on every device (diagnostics, tools/bench_inst_freq.py's other leg)."""
+    return os.environ.get("RH_INST_FREQ", "1") != "0"
+
+
+def inst_freq_compose(x: Tensor, y: Tensor, windows, scales, weighted: bool):
+    """WeightedInstantaneousSpectralDistance.forward as the reference states it (rave/core.py:347-412), cumsum included, on
+    whatever device and dtype the (rows, T) signals have; ``windows`` already carry the ``normalized`` factor.  What CPU
+    tensors, other dtypes and unbuilt scales take."""
+    import math
+
+    def inst_freq(phi):
+        d = phi[..., 1:] - phi[..., :-1]
+        d = ((d + math.pi) % (2 * math.pi) - math.pi).cumsum(-1)
+        return d[..., 1:] - d[..., :-1]
+
+    spectral, phase = 0., 0.
+    for n, win in zip(scales, windows):
+        n = int(n)
+        sx, sy = (torch.stft(s, n, hop_length=n // 4, win_length=n, window=win.to(s.dtype), center=True, pad_mode="reflect",
+                             normalized=False, onesided=True, return_complex=True) for s in (x, y))
+        ax, ay = sx.abs(), sy.abs()
+        lin = ((ax - ay) * (ax - ay)).mean() / (ax * ax).mean()
+        log = (torch.log1p(ax) - torch.log1p(ay)).abs().mean()
+        spectral = spectral + lin + log
+        fx, fy = inst_freq(sx.angle()), inst_freq(sy.angle())
+        if weighted:
+            mask = torch.clip(torch.log1p(ax[..., 2:]), 0, 1)
+            fx, fy = fx * mask, fy * mask
+        phase = phase + ((fx - fy) * (fx - fy)).mean()
+    return spectral, phase
+
+
+class _MultiScaleInstFreqFn(torch.autograd.Function):
+    """WeightedInstantaneousSpectralDistance over ALL scales as one autograd node (rave/core.py:347-412): per scale one
+    rh_inst_freq_loss_fwd_f32 launch, one ordered finalize for all of them, the two distances as two device scalars; backward:
+    per scale one rh_inst_freq_loss_bwd_f32 launch accumulating into one dx / dy buffer.  Nothing but the two waveforms and 4
+    sums per scale is saved.  ``if_outs``: per scale a (rows, 2, bins, frames - 2) buffer for the kernel's IF values
+    (diagnostics), or None."""
+
+    @staticmethod
+    def forward(ctx, x, y, weighted: bool, scales, if_outs, *windows):
+        x = _chk(x, "x"); y = _chk(y, "y")
+        if x.shape != y.shape or x.dim() != 2:
+            raise RuntimeError("rave_amd multiscale_inst_freq_distance: expects two (rows, T) tensors of equal shape")
+        rows, t = x.shape
+        if not inst_freq_supported(scales, t, rows):
+            raise RuntimeError(f"rave_amd multiscale_inst_freq_distance: scales {tuple(scales)} at T = {t}, rows = {rows} are not "
+                               "built (rh_inst_freq_loss_supported)")
+        s = L.stream()
+        dev = x.device
+        ns = len(scales)
+        sums = torch.empty(ns, 4, device=dev, dtype=torch.float32)
+        parts, inv_n = [], []
+        for i, (n_fft, win) in enumerate(zip(scales, windows)):
+            win = _chk(win, "window")
+            nbytes = L.lib.rh_inst_freq_loss_workspace_bytes(n_fft, t, rows)
+            ws = torch.empty(max(nbytes // 4, 1), device=dev, dtype=torch.float32)
+            dbg = None if if_outs is None else L.ptr(if_outs[i])
+            L.check(L.lib.rh_inst_freq_loss_fwd_f32(L.ptr(x), L.ptr(y), L.ptr(win), _twiddle64(n_fft, dev).data_ptr(), rows, t, n_fft,
+                                                    int(weighted), dbg, L.ptr(ws), nbytes, s), "inst_freq_loss_fwd")
+            parts.append((ws, nbytes))
+            nf, nb = t // (n_fft // 4) + 1, rows * (n_fft // 2 + 1)
+            inv_n += [1.0 / (nb * nf), 1.0 / (nb * (nf - 2))]
+        key = (tuple(inv_n), str(dev))
+        if key not in _INV_N and not torch.cuda.is_current_stream_capturing():
+            _INV_N[key] = torch.tensor(inv_n, dtype=torch.float32, device=dev)
+        inv = _inv_n_cached(tuple(inv_n), dev)
+        out = torch.empty(2, device=dev, dtype=torch.float32)
+        pp = (C.c_void_p * ns)(*[w.data_ptr() for w, _ in parts])
+        nb = (C.c_int64 * ns)(*[b for _, b in parts])
+        L.check(L.lib.rh_inst_freq_loss_finalize_all_f32(pp, nb, ns, L.ptr(inv), L.ptr(sums), L.ptr(out), s), "inst_freq_loss_finalize_all")
+        ctx.save_for_backward(sums, *windows, x, y)
+        ctx.meta = (rows, t, bool(weighted), tuple(int(v) for v in scales))
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_spectral, g_phase):
+        rows, t, weighted, scales = ctx.meta
+        ns = len(scales)
+        sums = ctx.saved_tensors[0]
+        windows = ctx.saved_tensors[1:1 + ns]
+        x, y = ctx.saved_tensors[1 + ns:]
+        dev = x.device
+        g = torch.zeros(2, device=dev, dtype=torch.float32)
+        for k, gk in enumerate((g_spectral, g_phase)):
+            if gk is not None:
+                g[k].copy_(gk.reshape(()))
+        s = L.stream()
+        need = (ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        outs = [torch.empty(rows, t, device=dev, dtype=torch.float32) if nd else None for nd in need]
+        for i, n_fft in enumerate(scales):
+            L.check(L.lib.rh_inst_freq_loss_bwd_f32(L.ptr(x), L.ptr(y), L.ptr(windows[i]), _twiddle64(n_fft, dev).data_ptr(), rows, t, n_fft,
+                                                    int(weighted), sums[i].data_ptr(), L.ptr(g),
+                                                    None if outs[0] is None else L.ptr(outs[0]),
+                                                    None if outs[1] is None else L.ptr(outs[1]), 1 if i > 0 else 0, s), "inst_freq_loss_bwd")
+        return (outs[0], outs[1], None, None, None) + (None,) * ns
+
+
+def multiscale_inst_freq_distance(x: Tensor, y: Tensor, windows, scales, weighted: bool, debug_if: bool = False):
+    """(spectral_distance, phase_distance) of WeightedInstantaneousSpectralDistance (rave/core.py:347-412) for the target x and
+    the prediction y, both (rows, T) f32 on the GPU, differentiable in both: the sum over the scales of
+    mean((|X|-|Y|)^2)/mean(|X|^2) + mean(|log1p|X| - log1p|Y||), and of mean((m IFx - m IFy)^2) with
+    IF = wrap(diff(angle)) along the frames (rave_amd/csrc/inst_freq_loss.hip).  ``windows``: one (n_fft,) window per scale, the
+    ``normalized`` factor folded in.  ``debug_if``: also returns, per scale, the kernel's unweighted IF values as
+    (rows, 2, n_fft / 2 + 1, frames - 2) -- [:, 0] of x, [:, 1] of y (tests)."""
+    scales = tuple(int(s) for s in scales)
+    if_outs = None
+    if debug_if:
+        rows, t = x.shape
+        if_outs = [torch.zeros(rows, 2, n // 2 + 1, t // (n // 4) - 1, device=x.device, dtype=torch.float32) for n in scales]
+    sd, pd = _MultiScaleInstFreqFn.apply(x, y, bool(weighted), scales, if_outs, *windows)
+    return (sd, pd, if_outs) if debug_if else (sd, pd)
 
 
 # --------------------------------------------------------------------------- mel-spectrogram encoder input
