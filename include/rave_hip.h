@@ -860,6 +860,42 @@ int rh_feature_matching_fwd_f32(const rh_fm_item* items, int32_t n_items, int32_
 int rh_feature_matching_bwd_f32(const rh_fm_item* items, int32_t n_items, int32_t relative, const float* sums,
                                 const float* grad_out, rh_stream_t stream);
 
+/* The GAN objectives (rave/core.py:151-170: hinge_gan, ls_gan, nonsaturating_gan) summed over the discriminator heads as the
+ * training step accumulates them (rave/model.py:354-376), with the logged pred_real / pred_fake of the same loop.
+ * Item i is one head: `real` and `fake` are two dense blocks of n f32 scores each, in any element order (a mean does not care,
+ * and bwd writes d_real / d_fake in the same memory order); for an unsplit (2B, ...) score map fake = real + n.  Every pointer
+ * may be any 4-byte aligned address (16-byte accesses are used where the pointers and n allow them; the bits are the same).
+ * mode: RH_GAN_HINGE      dis = mean(relu(1 - r) + relu(1 + f)),       adv = mean(-f)
+ *       RH_GAN_LS         dis = mean((r - 1)^2 + f^2),                  adv = mean((f - 1)^2)
+ *       RH_GAN_NONSAT     p = clamp(sigmoid(s), 1e-7, 1 - 1e-7), both bounds rounded to f32 (sigmoid = 1 / (1 + expf(-s)));
+ *                         dis = mean(-(logf(p_r) + logf(1 - p_f))),     adv = mean(-logf(p_f))
+ * fwd: sums[4 i + {0, 1, 2, 3}] = head i's dis, adv, mean(r), mean(f);  out[0 .. 3] = loss_dis, loss_adv, pred_real, pred_fake
+ * = the SUMS of those over the heads (not averages).  Two launches: per-workgroup partials into `workspace`
+ * (rh_gan_loss_workspace_bytes; contents irrelevant before and after), then one ordered finalize.
+ * bwd: grad_out[0 .. 1] (device memory) = d / d loss_dis, d / d loss_adv; writes d_real and d_fake of every head (overwritten,
+ * not accumulated) in one launch; pred_* are logged values and carry no gradient.  Gates as ATen's: relu passes where its
+ * argument is > 0 (0 at equality); the clamp passes where lo <= sigmoid(s) <= hi, so the gradient is exactly 0 wherever it
+ * changed the value.  No atomics, one fixed order of additions: bit-identical from run to run.
+ * `items` is a HOST array (device pointers inside) consumed during the call.  Refused before anything is launched: a null
+ * table, a null real / fake (bwd: d_real / d_fake as well), null workspace / sums / out / grad_out, n <= 0 (RH_ERR_INVALID);
+ * n_items outside 1 ... 80, an unknown mode (RH_ERR_UNSUPPORTED; rh_gan_loss_supported answers 1 / 0 for the pair); a
+ * workspace smaller than rh_gan_loss_workspace_bytes (RH_ERR_WORKSPACE; that query returns -1 for a null table, n_items outside 1 ... 80 or an n <= 0). */
+#define RH_GAN_HINGE 0
+#define RH_GAN_LS 1
+#define RH_GAN_NONSAT 2
+typedef struct rh_gan_item {
+    const float* real;
+    const float* fake;
+    float* d_real;
+    float* d_fake;
+    int64_t n;
+} rh_gan_item;
+int rh_gan_loss_supported(int32_t mode, int32_t n_items);
+int64_t rh_gan_loss_workspace_bytes(const rh_gan_item* items, int32_t n_items);
+int rh_gan_loss_fwd_f32(const rh_gan_item* items, int32_t n_items, int32_t mode, void* workspace, int64_t workspace_bytes,
+                        float* sums, float* out, rh_stream_t stream);
+int rh_gan_loss_bwd_f32(const rh_gan_item* items, int32_t n_items, int32_t mode, const float* grad_out, rh_stream_t stream);
+
 /* VariationalEncoder.reparametrize (rave/blocks.py:727-745): z (batch, 2c, l) = [mean | scale] along dim 1, eps (batch, c, l)
  * the noise draw;  std = softplus(scale) + 1e-4,  zs = eps * std + mean,
  * kl[0] = (mean^2 + std^2 - log(std^2) - 1).sum(1).mean().  bwd: dz from dzs (may be NULL) and the scalar dkl (may be NULL). */

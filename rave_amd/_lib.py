@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RAVE_HIP_LIB") or os.path.join(_HERE, "librave_hip.so")
 
 ACT_NONE, ACT_LEAKY, ACT_SNAKE = 0, 1, 2
+GAN_HINGE, GAN_LS, GAN_NONSAT = 0, 1, 2      # RH_GAN_* (include/rave_hip.h)
 
 
 class ConvDesc(C.Structure):
@@ -63,6 +64,11 @@ class LossItem(C.Structure):
 class FmItem(C.Structure):
     """Mirror of ``rh_fm_item`` (include/rave_hip.h)."""
     _fields_ = [("f", C.c_void_p), ("df", C.c_void_p), ("half", C.c_int64), ("w", C.c_float)]
+
+
+class GanItem(C.Structure):
+    """Mirror of ``rh_gan_item`` (include/rave_hip.h)."""
+    _fields_ = [("real", C.c_void_p), ("fake", C.c_void_p), ("d_real", C.c_void_p), ("d_fake", C.c_void_p), ("n", C.c_int64)]
 
 
 class Conv2dDesc(C.Structure):
@@ -158,6 +164,10 @@ def _load() -> C.CDLL:
         "rh_feature_matching_workspace_bytes": ([C.POINTER(FmItem), I32], I64),
         "rh_feature_matching_fwd_f32": ([C.POINTER(FmItem), I32, I32, P, I64, P, P, P], C.c_int),
         "rh_feature_matching_bwd_f32": ([C.POINTER(FmItem), I32, I32, P, P, P], C.c_int),
+        "rh_gan_loss_supported": ([I32, I32], C.c_int),
+        "rh_gan_loss_workspace_bytes": ([C.POINTER(GanItem), I32], I64),
+        "rh_gan_loss_fwd_f32": ([C.POINTER(GanItem), I32, I32, P, I64, P, P, P], C.c_int),
+        "rh_gan_loss_bwd_f32": ([C.POINTER(GanItem), I32, I32, P, P], C.c_int),
         "rh_reparam_workspace_bytes": ([], I64),
         "rh_reparam_fwd_f32": ([P, P, I32, I32, I32, P, P, P, I64, P], C.c_int),
         "rh_reparam_bwd_f32": ([P, P, P, P, I32, I32, I32, P, P], C.c_int),

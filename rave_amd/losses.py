@@ -31,10 +31,53 @@ def mean_difference(target, value, norm: str = "L1", relative: bool = False):
     raise Exception(f"Norm must be either L1 or L2, got {norm}")
 
 
+def _gan_kernel(score_real, score_fake) -> bool:
+    """The three objectives below take the HIP kernel (rave_amd/csrc/gan_loss.hip, one head per call: two launches forward, one
+    backward) on float32 scores of equal shape on one GPU; CPU tensors, other dtypes, unequal (broadcasting) shapes and
+    ``RH_GAN_LOSS=0`` run the reference's torch composition."""
+    if not (torch.is_tensor(score_real) and torch.is_tensor(score_fake) and score_real.is_cuda and score_fake.is_cuda
+            and score_real.dtype == torch.float32 and score_fake.dtype == torch.float32
+            and score_real.device == score_fake.device
+            and score_real.shape == score_fake.shape and score_real.numel() > 0):
+        return False
+    from . import ops
+    return ops.gan_loss_on()
+
+
+def _gan_kernel_call(score_real, score_fake, mode: int):
+    from . import ops
+    return ops.gan_losses([(score_real, score_fake)], mode)[:2]
+
+
 def hinge_gan(score_real, score_fake):
     """rave/core.py:151-155."""
+    if _gan_kernel(score_real, score_fake):
+        return _gan_kernel_call(score_real, score_fake, hinge_gan.gan_mode)
     loss_dis = (torch.relu(1 - score_real) + torch.relu(1 + score_fake)).mean()
     return loss_dis, -score_fake.mean()
+
+
+def ls_gan(score_real, score_fake):
+    """rave/core.py:158-162."""
+    if _gan_kernel(score_real, score_fake):
+        return _gan_kernel_call(score_real, score_fake, ls_gan.gan_mode)
+    loss_dis = ((score_real - 1).pow(2) + score_fake.pow(2)).mean()
+    return loss_dis, (score_fake - 1).pow(2).mean()
+
+
+def nonsaturating_gan(score_real, score_fake):
+    """rave/core.py:165-170: sigmoid, then clamp, then log -- the saturation at -log 1e-7 is part of the objective."""
+    if _gan_kernel(score_real, score_fake):
+        return _gan_kernel_call(score_real, score_fake, nonsaturating_gan.gan_mode)
+    score_real = torch.clamp(torch.sigmoid(score_real), 1e-7, 1 - 1e-7)
+    score_fake = torch.clamp(torch.sigmoid(score_fake), 1e-7, 1 - 1e-7)
+    loss_dis = -(torch.log(score_real) + torch.log(1 - score_fake)).mean()
+    return loss_dis, -torch.log(score_fake).mean()
+
+
+# the kernel mode of each objective (RH_GAN_* of include/rave_hip.h): how RAVE.training_step recognises them
+hinge_gan.gan_mode, ls_gan.gan_mode, nonsaturating_gan.gan_mode = 0, 1, 2
+GAN_LOSSES = {"hinge": hinge_gan, "ls": ls_gan, "nonsaturating": nonsaturating_gan}
 
 
 class MultiScaleSTFT(nn.Module):

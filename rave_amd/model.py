@@ -257,6 +257,35 @@ class RAVE(nn.Module):
             total = part if total is None else total + part
         return total
 
+    def _fused_gan_losses(self, features):
+        """(loss_dis, loss_adv, pred_real, pred_fake) of rave/model.py:354-376 in one HIP call over the last (score) map of every
+        discriminator head (rave_amd.ops.gan_losses: two launches forward, one backward) when ``gan_loss`` is one of
+        losses.hinge_gan / ls_gan / nonsaturating_gan -- the function itself, a ``partial`` of it without arguments, or a wrapper
+        that carries its ``gan_mode`` attribute -- and every score map is a float32 GPU tensor with an even, dense batch
+        dimension; None -> the per-head loop runs.  ``RH_GAN_LOSS=0`` disables."""
+        fn = self.gan_loss
+        if isinstance(fn, partial) and not fn.args and not fn.keywords:
+            fn = fn.func
+        mode = getattr(fn, "gan_mode", None)
+        if not isinstance(mode, int) or mode not in (0, 1, 2):
+            return None
+        from . import ops
+        if not ops.gan_loss_on():
+            return None
+        heads = []
+        for scale in features:
+            s = scale[-1] if len(scale) else None
+            if not (torch.is_tensor(s) and s.is_cuda and s.dtype == torch.float32 and ops._dense_batch_major(s)):
+                return None
+            heads.append(s)
+        if not heads:
+            return None
+        total = None
+        for i in range(0, len(heads), 80):         # one kernel-argument table holds 80 heads
+            part = ops.gan_losses(heads[i:i + 80], mode)
+            total = part if total is None else tuple(a + b for a, b in zip(total, part))
+        return total
+
     @staticmethod
     def _join_side() -> None:
         """The weight-gradient side stream (rave_amd.ops._OnSide) is joined by a callback at the end of every backward pass;
@@ -373,16 +402,24 @@ class RAVE(nn.Module):
             feature_real, feature_fake = self.split_features(features)
             loss_dis = 0
             loss_adv = 0
+            pred_real = 0
+            pred_fake = 0
             fused_fm = self._fused_feature_matching(features)
+            fused_gan = self._fused_gan_losses(features)
             for scale_real, scale_fake in zip(feature_real, feature_fake):
                 if fused_fm is None:
                     current = sum(map(self.feature_matching_fun,
                                       scale_real[self.num_skipped_features:],
                                       scale_fake[self.num_skipped_features:])) / len(scale_real[self.num_skipped_features:])
                     feature_matching_distance = feature_matching_distance + current
-                _dis, _adv = self.gan_loss(scale_real[-1], scale_fake[-1])
-                loss_dis = loss_dis + _dis
-                loss_adv = loss_adv + _adv
+                if fused_gan is None:
+                    _dis, _adv = self.gan_loss(scale_real[-1], scale_fake[-1])
+                    pred_real = pred_real + scale_real[-1].detach().mean()       # rave/model.py:372-373 (logged only)
+                    pred_fake = pred_fake + scale_fake[-1].detach().mean()
+                    loss_dis = loss_dis + _dis
+                    loss_adv = loss_adv + _adv
+            if fused_gan is not None:
+                loss_dis, loss_adv, pred_real, pred_fake = fused_gan
             feature_matching_distance = fused_fm if fused_fm is not None else feature_matching_distance / len(feature_real)
         else:
             loss_dis = torch.zeros((), device=x_raw.device, dtype=x_raw.dtype)     # (no host-to-device copy)
@@ -444,6 +481,9 @@ class RAVE(nn.Module):
                 pr.invalidate()
         self.logged = dict(loss_gen)
         self.logged["loss_dis"] = loss_dis
+        if self.warmed_up:                      # rave/model.py:418-421
+            self.logged["pred_real"] = pred_real
+            self.logged["pred_fake"] = pred_fake
         return self.logged
 
 
@@ -821,7 +861,8 @@ def build_v2(n_channels: int = 1, capacity: int = 96, ratios=(4, 4, 4, 2), laten
              codebook_size: int = 1024, log_epsilon: float = 1e-7, num_skipped_features: int = 1,
              spectral_capacity: int = 32, gru_layers: int = 0, mel_input: bool = False, n_fft: int = 2048,
              hop_length: int = 256, n_mels: int = 128, encoder_ratios=(2, 2, 2), encoder_dilations=(1,),
-             latent_analysis: bool = False, hip_frontend: bool = False, phase_distance: bool = False) -> RAVE:
+             latent_analysis: bool = False, hip_frontend: bool = False, phase_distance: bool = False,
+             gan_loss: str = "hinge") -> RAVE:
     """configs/v1.gin + configs/v2.gin transcribed (cf. oracle/ref_models.py for the citations).
     ``snake`` / ``adain`` add the generator-side overlays of configs/v3.gin (snake.gin: every activation
     -> blocks.Snake; adain.gin: AdaptiveInstanceNormalization before every unit); ``causal`` =
@@ -838,7 +879,11 @@ def build_v2(n_channels: int = 1, capacity: int = 96, ratios=(4, 4, 4, 2), laten
     rave_amd/csrc/spectrogram.hip (the gin route: rave_amd/configs/mi355x_spectrogram*.gin); off by default.
     ``phase_distance`` binds the fullband distance to losses.WeightedInstantaneousSpectralDistance (weighted, over the
     normalised complex multi-scale STFT) as rave_amd/configs/mi355x_phase.gin does: the step then logs and trains on
-    ``fullband_phase_distance`` as well; off by default."""
+    ``fullband_phase_distance`` as well; off by default.
+    ``gan_loss``: "hinge" (every stock config), "ls" or "nonsaturating" -- losses.hinge_gan / ls_gan / nonsaturating_gan
+    (rave/core.py:151-170; the gin route: rave_amd/configs/mi355x_gan_loss.gin)."""
+    if gan_loss not in losses.GAN_LOSSES:
+        raise ValueError(f"build_v2: gan_loss {gan_loss!r}, expected one of {sorted(losses.GAN_LOSSES)}")
     ratios = list(ratios)
     spectrogram = None
     if mel_input:
@@ -916,7 +961,7 @@ def build_v2(n_channels: int = 1, capacity: int = 96, ratios=(4, 4, 4, 2), laten
     model = RAVE(latent_size=latent_size, sampling_rate=sampling_rate,
                  pqmf=partial(pqmf.CachedPQMF, attenuation=100, n_band=n_band),
                  encoder=enc, decoder=dec, discriminator=disc, phase_1_duration=1000000,
-                 gan_loss=losses.hinge_gan, valid_signal_crop=True,
+                 gan_loss=losses.GAN_LOSSES[gan_loss], valid_signal_crop=True,
                  feature_matching_fun=partial(losses.mean_difference, norm="L1", relative=True),
                  num_skipped_features=num_skipped_features, audio_distance=full_dist, multiband_audio_distance=dist,
                  weights={"feature_matching": 20}, update_discriminator_every=update_discriminator_every,

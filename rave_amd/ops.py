@@ -1822,6 +1822,153 @@ def feature_matching(features, weights, relative: bool) -> Tensor:
     return _FeatureMatchingFn.apply(bool(relative), tuple(float(w) for w in weights), *features)
 
 
+# --------------------------------------------------------------------------- GAN objectives (GAN phase)
+GAN_MODES = {"hinge": L.GAN_HINGE, "ls": L.GAN_LS, "nonsaturating": L.GAN_NONSAT}
+
+
+def gan_loss_on() -> bool:
+    """RH_GAN_LOSS=0: the GAN objectives as the reference's chains of ATen operations (rave_amd.losses)."""
+    import os
+    return os.environ.get("RH_GAN_LOSS", "1") != "0"
+
+
+def _dense_any_order(t: Tensor) -> bool:
+    """True if ``t``'s memory is one dense block (its dims in any order): a half of a ``_dense_batch_major`` tensor split
+    along dim 0 is one."""
+    if t.numel() == 0:
+        return False
+    if t.is_contiguous():
+        return True
+    acc = 1
+    for st, sz in sorted((t.stride(i), t.shape[i]) for i in range(t.dim()) if t.shape[i] > 1):
+        if st != acc:
+            return False
+        acc *= sz
+    return True
+
+
+_GAN_ZERO = {}
+
+
+def _gan_zero(dev) -> Tensor:
+    """A 0-d zero on ``dev`` standing for the gradient of the objective nobody differentiated (kept per device; one made while
+    a graph is being recorded belongs to that graph's pool and is not kept)."""
+    z = _GAN_ZERO.get(dev)
+    if z is None:
+        z = torch.zeros((), device=dev, dtype=torch.float32)
+        if not torch.cuda.is_current_stream_capturing():
+            _GAN_ZERO[dev] = z
+    return z
+
+
+class _GanLossFn(torch.autograd.Function):
+    """(loss_dis, loss_adv, pred_real, pred_fake) of rave/model.py:354-376 over every discriminator head,
+    rh_gan_loss_{fwd,bwd}_f32: two launches forward and one backward instead of ~10 ATen dispatches per head each way.
+    ``layout[i]``: True = tensor i is an unsplit (2B, ...) score map, False = tensors i, i + 1 are a (real, fake) pair."""
+
+    @staticmethod
+    def forward(ctx, mode: int, layout, *scores):
+        for t in scores:
+            if not t.is_cuda or t.dtype != torch.float32:
+                raise RuntimeError("rave_amd gan_losses: scores must be float32 tensors on the GPU")
+            if t.device != scores[0].device:
+                raise RuntimeError(f"rave_amd gan_losses: all scores must live on one GPU, got {scores[0].device} and {t.device}")
+        it = iter(scores)
+        heads = []                      # (tensors kept for backward, real ptr, fake ptr, n)
+        for unsplit in layout:
+            if unsplit:
+                t = next(it)
+                if t.dim() < 1 or t.shape[0] % 2 or t.numel() == 0:
+                    raise RuntimeError("rave_amd gan_losses: an unsplit score map needs an even, non-empty batch dimension")
+                # NOT _chk(): permuted views of dense period-major maps are read, and their gradients written, in their own
+                # memory order (as _FeatureMatchingFn does)
+                t = t if _dense_batch_major(t) else t.contiguous()
+                n = t.numel() // 2
+                heads.append(((t,), t.data_ptr(), t.data_ptr() + 4 * n, n))
+            else:
+                r, f = next(it), next(it)
+                if r.numel() != f.numel() or r.numel() == 0:
+                    raise RuntimeError("rave_amd gan_losses: the real and the fake scores of a head must have the same, non-zero "
+                                       f"number of elements, got {tuple(r.shape)} and {tuple(f.shape)}")
+                r = r if _dense_any_order(r) else r.contiguous()
+                f = f if _dense_any_order(f) else f.contiguous()
+                heads.append(((r, f), r.data_ptr(), f.data_ptr(), r.numel()))
+        n_heads = len(heads)
+        if not L.lib.rh_gan_loss_supported(int(mode), n_heads):
+            raise RuntimeError(f"rave_amd gan_losses: mode {mode} with {n_heads} heads is not built (modes 0 ... 2, 1 ... 80 heads)")
+        dev = scores[0].device
+        arr = (L.GanItem * n_heads)()
+        for a, (_, rp, fp, n) in zip(arr, heads):
+            a.real, a.fake, a.d_real, a.d_fake, a.n = rp, fp, None, None, n
+        nbytes = L.lib.rh_gan_loss_workspace_bytes(arr, n_heads)
+        if nbytes < 0:
+            raise RuntimeError("rave_amd gan_losses: bad head table")
+        ws = torch.empty(max(nbytes // 4, 1), device=dev, dtype=torch.float32)
+        sums = torch.empty(n_heads, 4, device=dev, dtype=torch.float32)
+        out = torch.empty(4, device=dev, dtype=torch.float32)
+        L.check(L.lib.rh_gan_loss_fwd_f32(arr, n_heads, int(mode), L.ptr(ws), nbytes, L.ptr(sums), L.ptr(out), L.stream()),
+                "gan_loss_fwd")
+        ctx.save_for_backward(*[t for kept in heads for t in kept[0]])
+        ctx.meta = (int(mode), tuple(bool(u) for u in layout))
+        ctx.set_materialize_grads(False)
+        dis, adv, pr, pf = out.unbind(0)
+        ctx.mark_non_differentiable(pr, pf)
+        return dis, adv, pr, pf
+
+    @staticmethod
+    def backward(ctx, g_dis, g_adv, _g_pr, _g_pf):
+        mode, layout = ctx.meta
+        ts = ctx.saved_tensors
+        if g_dis is None and g_adv is None:
+            return (None, None) + (None,) * len(ts)
+        dev = ts[0].device
+        zero = None if (g_dis is not None and g_adv is not None) else _gan_zero(dev)
+        g = torch.stack([(zero if v is None else v.reshape(()).float()) for v in (g_dis, g_adv)])
+        n_heads = len(layout)
+        arr = (L.GanItem * n_heads)()
+        grads = []
+        k = 0
+        for a, unsplit in zip(arr, layout):
+            if unsplit:
+                t = ts[k]
+                k += 1
+                d = torch.empty_like(t)        # same strides as t (dense): element j of the block is element j of t's block
+                n = t.numel() // 2
+                a.real, a.fake, a.d_real, a.d_fake, a.n = t.data_ptr(), t.data_ptr() + 4 * n, d.data_ptr(), d.data_ptr() + 4 * n, n
+                grads.append(d)
+            else:
+                r, f = ts[k], ts[k + 1]
+                k += 2
+                dr, df = torch.empty_like(r), torch.empty_like(f)
+                a.real, a.fake, a.d_real, a.d_fake, a.n = r.data_ptr(), f.data_ptr(), dr.data_ptr(), df.data_ptr(), r.numel()
+                grads.extend((dr, df))
+        L.check(L.lib.rh_gan_loss_bwd_f32(arr, n_heads, mode, L.ptr(g), L.stream()), "gan_loss_bwd")
+        return (None, None) + tuple(grads)
+
+
+def gan_losses(heads, mode):
+    """(loss_dis, loss_adv, pred_real, pred_fake): the objective ``mode`` ("hinge", "ls", "nonsaturating" or its RH_GAN_* number)
+    of rave/core.py:151-170 and the mean scores, each summed over ``heads`` as rave/model.py:354-376 sums them.  A head is an
+    unsplit score map (2B, ...), real half of the batch first, or a ``(real, fake)`` pair of equally many scores.  At most 80
+    heads per call; pred_* carry no gradient."""
+    if isinstance(mode, str):
+        if mode not in GAN_MODES:
+            raise ValueError(f"rave_amd gan_losses: mode {mode!r}, expected one of {sorted(GAN_MODES)}")
+        mode = GAN_MODES[mode]
+    layout, flat = [], []
+    for h in heads:
+        if torch.is_tensor(h):
+            layout.append(True)
+            flat.append(h)
+        else:
+            r, f = h
+            layout.append(False)
+            flat.extend((r, f))
+    if not flat:
+        raise RuntimeError("rave_amd gan_losses: no heads")
+    return _GanLossFn.apply(mode, tuple(layout), *flat)
+
+
 class _LossCombineFn(torch.autograd.Function):
     """(total, scaled): scaled_i = w1_i * value_i, total = sum_i scaled_i * w2_i -- rh_loss_combine_fwd/bwd_f32."""
 
