@@ -716,6 +716,49 @@ int rh_mel_diff_bwd_f32(const float* dmel, const float* x, const float* window, 
                         const int32_t* bins, int64_t rows, int32_t t_len, int32_t n_fft, int32_t hop, int32_t n_mels,
                         int32_t center, int32_t power, float scale, float* dx, rh_stream_t stream);
 
+/* The plain SpectralDistance of the Encodec-style loss on one STFT scale (rave/core.py:446-490 without `mel`: torchaudio
+ * Spectrogram(n_fft, hop = n_fft / 4, power, normalized, center=False) of both signals, then mean_difference(y, x, norm),
+ * rave/core.py:236-252, summed over the norms; EncodecAudioDistance, rave/core.py:415-433, sums it over its scales) with the
+ * transform INSIDE the kernel.  x, y (rows, t_len) f32, two buffers that do not overlap; window (n_fft: the plain window);
+ * twiddle as for rh_stft_loss_fwd_f32 (8-byte aligned).  frames = (t_len - n_fft) / hop + 1, bins = n_fft / 2 + 1,
+ *   A = |scale * rfft(window * frame(y))|^power,  B = the same of x,  power 1 or 2,
+ * scale = 1 / sqrt(sum(window^2)) for `normalized=True`, else 1: the caller computes it, as for rh_mel_diff_*.  A frame of x
+ * and the same frame of y ride one complex transform, equalised by a power of two; a pair of frames that are equal sample by
+ * sample has A - B = 0 by definition (two transforms of the same samples agree to the bit, the two halves of one do not), so
+ * identical signals have distance exactly 0 and a zero gradient.
+ * rh_spec_dist_fwd_f32 (replaces the unfold, window product, rocFFT, abs / pow and the reductions of rave/core.py:470-490):
+ *   per workgroup (a span of frames of one row, walked in order) a fixed-tree partial of sum |A - B| and sum (A - B)^2, in
+ *   (row, workgroup) order in `workspace` (rh_spec_dist_workspace_bytes).  No spectrum is written anywhere.
+ * rh_spec_dist_finalize_all_f32 (replaces mean_difference's launches and the sum over the scales, rave/core.py:415-433): ONE
+ *   launch for all scales of a distance adds the partials in a fixed order: sums (n_scales x 2) and
+ *   total = sum_s (use_l1 * sums[s][0] + use_l2 * sums[s][1]) * inv_n[s]; inv_n: DEVICE array, 1 / (rows bins frames) per scale;
+ *   partials[s] / partial_bytes[s]: HOST arrays (the workspaces of the forward calls); 1 .. 8 scales.
+ * rh_spec_dist_bwd_f32 (replaces autograd through all of the above): a workgroup owns a span of dx / dy, recomputes the spectra
+ *   of every frame that covers it and applies the cotangent grad_out[0] * inv_n * (use_l1 sign(A - B) + use_l2 2 (A - B)) with
+ *   respect to A, negated for B (grad_out: one DEVICE scalar; sign(0) = 0), the power (scale S / |S| for power 1, exactly 0
+ *   where |S| = 0 as torch's abs; 2 scale^2 S for power 2), the transposed real DFT, the window and the overlap-add.  Writes
+ *   (accumulate = 0) or adds (!= 0: the scales of one distance sum in place) dx and dy; either may be NULL -- both gradients ride
+ *   one inverse transform, a NULL side adds none and the other side's bits do not depend on it.  Samples that no frame covers
+ *   (the uncentred tail) get exactly 0.  No atomics: one writer and one fixed order of additions per sample and per sum, the
+ *   bits are reproducible; every launch can be captured.
+ * Sizes (rh_spec_dist_supported answers 1 / 0; a host function): n_fft a power of two in 128 .. 2048, hop = n_fft / 4,
+ * n_fft <= t_len <= 2^30, 0 < rows < 65536, power in {1, 2}, at least one norm -- anything else is RH_ERR_UNSUPPORTED; null
+ * pointers, a misaligned twiddle table, overlapping x / y and a scale that is not positive and finite are RH_ERR_INVALID;
+ * nothing is enqueued in any of these cases.  x, y, dx and dy need only be 4-byte aligned.  The backward kernel's dynamic LDS
+ * never exceeds the 150 KiB cap of rh_stft_loss_bwd_f32's plan (rh_spec_dist_plan_info: out6 as rh_stft_loss_plan_info). */
+int rh_spec_dist_supported(int32_t n_fft, int32_t hop, int32_t t_len, int64_t rows, int32_t power);
+int64_t rh_spec_dist_workspace_bytes(int32_t n_fft, int32_t t_len, int64_t rows);
+int rh_spec_dist_plan_info(int32_t n_fft, int32_t t_len, int64_t rows, int64_t* out6);
+int rh_spec_dist_fwd_f32(const float* x, const float* y, const float* window, const float* twiddle, int64_t rows,
+                         int32_t t_len, int32_t n_fft, int32_t power, float scale, void* workspace, int64_t workspace_bytes,
+                         rh_stream_t stream);
+int rh_spec_dist_finalize_all_f32(const float* const* partials, const int64_t* partial_bytes, int32_t n_scales,
+                                  const float* inv_n, int32_t use_l1, int32_t use_l2, float* sums, float* total,
+                                  rh_stream_t stream);
+int rh_spec_dist_bwd_f32(const float* x, const float* y, const float* window, const float* twiddle, int64_t rows,
+                         int32_t t_len, int32_t n_fft, int32_t power, float scale, int32_t use_l1, int32_t use_l2,
+                         const float* grad_out, float* dx, float* dy, int32_t accumulate, rh_stream_t stream);
+
 /* The complex spectrogram in front of the spectral discriminators, with its gradient:
  * torchaudio.transforms.Spectrogram(n_fft, hop_length, power=None, normalized, center) followed by
  * cat([s.real, s.imag], 1) (rave/discriminator.py:12-20,147-152, center = 0; rave/descript_discriminator.py:153-160,

@@ -218,6 +218,12 @@ def _load() -> C.CDLL:
         "rh_inst_freq_loss_fwd_f32": ([P, P, P, P, I64, I32, I32, I32, P, P, I64, P], C.c_int),
         "rh_inst_freq_loss_finalize_all_f32": ([C.POINTER(C.c_void_p), C.POINTER(I64), I32, P, P, P, P], C.c_int),
         "rh_inst_freq_loss_bwd_f32": ([P, P, P, P, I64, I32, I32, I32, P, P, P, P, I32, P], C.c_int),
+        "rh_spec_dist_supported": ([I32, I32, I32, I64, I32], C.c_int),
+        "rh_spec_dist_workspace_bytes": ([I32, I32, I64], I64),
+        "rh_spec_dist_plan_info": ([I32, I32, I64, C.POINTER(I64)], C.c_int),
+        "rh_spec_dist_fwd_f32": ([P, P, P, P, I64, I32, I32, I32, F, P, I64, P], C.c_int),
+        "rh_spec_dist_finalize_all_f32": ([C.POINTER(C.c_void_p), C.POINTER(I64), I32, P, I32, I32, P, P, P], C.c_int),
+        "rh_spec_dist_bwd_f32": ([P, P, P, P, I64, I32, I32, I32, F, I32, I32, P, P, P, I32, P], C.c_int),
         "rh_noise_synth_supported": ([I32, I32], C.c_int),
         "rh_noise_synth_table_f32": ([I32, I32, P], C.c_int),
         "rh_noise_synth_fwd_f32": ([P, P, P, I32, I32, I32, I32, I32, P, P], C.c_int),

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "librave_hip.so")
-SOURCES = ["api.cpp", "pqmf.hip", "pqmf_bands.hip", "pqmf_fold.hip", "pqmf_fold2.hip", "conv_igemm.hip", "conv_igemm_dma.hip", "conv_x6.hip", "conv_x6_i1_121.hip", "conv_x6_i1_221.hip", "conv_x6_i1_321.hip", "conv_x6_i1_122.hip", "conv_x6_i1_222.hip", "conv_x6_i1_322.hip", "conv_x6_i1_211.hip", "conv_x6_i1_311.hip", "conv_x6_i1_212.hip", "conv_x6_i1_312.hip", "conv_x6_i2_121.hip", "conv_x6_i2_221.hip", "conv_x6_i2_321.hip", "conv_x6_i2_122.hip", "conv_x6_i2_222.hip", "conv_x6_i2_322.hip", "conv_x6_i2_211.hip", "conv_x6_i2_311.hip", "conv_x6_i2_212.hip", "conv_x6_i2_312.hip", "conv_x6_i4_121.hip", "conv_x6_i4_221.hip", "conv_x6_i4_321.hip", "conv_x6_i4_122.hip", "conv_x6_i4_222.hip", "conv_x6_i4_322.hip", "conv_x6_i4_211.hip", "conv_x6_i4_311.hip", "conv_x6_i4_212.hip", "conv_x6_i4_312.hip", "unit_x6.hip", "conv_host.hip", "conv_wgrad.hip", "conv_wgrad_x6.hip", "conv_smallc.hip", "conv2d.hip", "conv2d_f32.hip", "conv2d_x6.hip", "conv2d_smallm.hip", "conv2d_smallc.hip", "wgrad2d_x6.hip", "vq.hip", "feed.hip", "feed_mask.hip", "misc.hip", "stft_loss.hip", "inst_freq_loss.hip", "mel.hip", "spectrogram.hip", "adam.hip", "ema.hip", "gru.hip", "feature_match.hip", "gan_loss.hip", "latent_stats.hip", "noise_synth.hip"]
+SOURCES = ["api.cpp", "pqmf.hip", "pqmf_bands.hip", "pqmf_fold.hip", "pqmf_fold2.hip", "conv_igemm.hip", "conv_igemm_dma.hip", "conv_x6.hip", "conv_x6_i1_121.hip", "conv_x6_i1_221.hip", "conv_x6_i1_321.hip", "conv_x6_i1_122.hip", "conv_x6_i1_222.hip", "conv_x6_i1_322.hip", "conv_x6_i1_211.hip", "conv_x6_i1_311.hip", "conv_x6_i1_212.hip", "conv_x6_i1_312.hip", "conv_x6_i2_121.hip", "conv_x6_i2_221.hip", "conv_x6_i2_321.hip", "conv_x6_i2_122.hip", "conv_x6_i2_222.hip", "conv_x6_i2_322.hip", "conv_x6_i2_211.hip", "conv_x6_i2_311.hip", "conv_x6_i2_212.hip", "conv_x6_i2_312.hip", "conv_x6_i4_121.hip", "conv_x6_i4_221.hip", "conv_x6_i4_321.hip", "conv_x6_i4_122.hip", "conv_x6_i4_222.hip", "conv_x6_i4_322.hip", "conv_x6_i4_211.hip", "conv_x6_i4_311.hip", "conv_x6_i4_212.hip", "conv_x6_i4_312.hip", "unit_x6.hip", "conv_host.hip", "conv_wgrad.hip", "conv_wgrad_x6.hip", "conv_smallc.hip", "conv2d.hip", "conv2d_f32.hip", "conv2d_x6.hip", "conv2d_smallm.hip", "conv2d_smallc.hip", "wgrad2d_x6.hip", "vq.hip", "feed.hip", "feed_mask.hip", "misc.hip", "stft_loss.hip", "inst_freq_loss.hip", "spec_dist.hip", "mel.hip", "spectrogram.hip", "adam.hip", "ema.hip", "gru.hip", "feature_match.hip", "gan_loss.hip", "latent_stats.hip", "noise_synth.hip"]
 HEADERS = ["common.hpp", "pqmf_bands.hpp", "multi_tensor.hpp", "conv_params.hpp", "f32_tile.hpp", "conv2d_plan.hpp", "conv2d_x6.hpp", "conv_x6_kernel.inc", "fft_lds.inc", os.path.join("..", "..", "include", "rave_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

@@ -187,11 +187,15 @@ class WaveformDistance(nn.Module):
 class SpectralDistance(nn.Module):
     """rave/core.py:446-490: the spectrum of both signals, then ``mean_difference(y, x, norm)`` summed over the norms.  Unused by
     the shipped configs (v1 ... v3, discrete use AudioDistanceV1); the Encodec-style loss binds it by gin
-    (rave_amd/configs/mi355x_encodec_mel.gin).
+    (rave_amd/configs/mi355x_encodec.gin, and mi355x_encodec_mel.gin for the mel variant).
 
-    Without ``mel``: torchaudio Spectrogram(n_fft, hop = n_fft / 4, power, normalized, center=False).  Framing is a strided view,
-    the transform rocFFT (torch.fft), the reductions ATen -- library code on whatever device the signals live on; nothing on
-    this path is a HIP kernel of this package.
+    Without ``mel``: torchaudio Spectrogram(n_fft, hop = n_fft / 4, power, normalized, center=False).  GPU float32 signals of
+    equal shape on one device, ``power`` 1 or 2, ``norm`` "L1", "L2" or both, at a built size (n_fft a power of two in
+    128 ... 2048, T >= n_fft: ``ops.spec_dist_supported``) run rave_amd/csrc/spec_dist.hip: the transform, ``|.|^power`` and both
+    reductions in one launch forward and one backward, no spectrum in memory (``ops.multiscale_spec_distance``; an
+    ``EncodecAudioDistance`` of such members runs all of its scales as one autograd node).  Everything else -- CPU tensors,
+    other dtypes, ``power=None`` (a complex spectrum), n_fft 32 / 64, ``RH_SPEC_DIST=0`` -- runs the torch composition
+    (``ops.spec_dist_compose``): a strided view, rocFFT, ATen reductions.
 
     ``mel=n``: torchaudio MelSpectrogram(sampling_rate, n_fft, hop = n_fft / 4, n_mels=n, power, normalized, center=False) as
     ``rave_amd.mel.DifferentiableMelSpectrogram`` (submodule ``mel_spec``, with torchaudio's two buffers): on GPU float32 signals
@@ -216,16 +220,25 @@ class SpectralDistance(nn.Module):
         """(..., T) -> (..., n_fft / 2 + 1, frames), torch.stft(center=False) layout; with ``mel``: (..., n_mels, frames)."""
         if "mel_spec" in self._modules:                                 # (the plain variant has no such attribute at all)
             return self.mel_spec(x)
-        w = self.window.to(x.dtype)
-        fr = x.unfold(-1, self.n_fft, self.hop) * w                     # (..., frames, n_fft): no padding (center=False)
-        s = torch.fft.rfft(fr, dim=-1).transpose(-1, -2)
-        if self.normalized:
-            s = s / w.pow(2.0).sum().sqrt()
-        if self.power is None:
-            return s
-        return s.abs() if self.power == 1.0 else s.abs().pow(self.power)
+        from . import ops
+        return ops.spec_dist_spectrum(x, self.window, self.n_fft, self.power, self.normalized)
+
+    def is_plain(self) -> bool:
+        return "mel_spec" not in self._modules
+
+    def refresh_host_caches(self) -> None:
+        """GraphedTrainingStep calls this before it records: the window's norm is read on the host here, outside the capture."""
+        if self.is_plain() and self.normalized and self.window.is_cuda:
+            from . import ops
+            ops._spec_dist_scale(self.window)
 
     def forward(self, x, y):
+        if self.is_plain():
+            from . import ops
+            if _spec_dist_kernel(x, y, [self]):
+                return ops.multiscale_spec_distance(x.reshape(-1, x.shape[-1]), y.reshape(-1, y.shape[-1]), [self.window],
+                                                    [self.n_fft], self.norm, self.power, self.normalized)
+            return ops.spec_dist_compose(x, y, self.window, self.n_fft, self.norm, self.power, self.normalized)
         x = self.spec(x)
         y = self.spec(y)
         distance = 0
@@ -234,8 +247,29 @@ class SpectralDistance(nn.Module):
         return distance
 
 
+def _spec_dist_kernel(x, y, members) -> bool:
+    """The plain ``SpectralDistance`` members (one, or all of an ``EncodecAudioDistance``) take the HIP kernels
+    (rave_amd/csrc/spec_dist.hip) on float32 signals of equal shape on one GPU when they agree in ``power`` (1 or 2),
+    ``normalized`` and ``norm`` ("L1", "L2" or both) and every scale is built; CPU tensors, other dtypes, unequal (broadcasting)
+    shapes, anything else and ``RH_SPEC_DIST=0`` run the torch composition."""
+    if not (torch.is_tensor(x) and torch.is_tensor(y) and x.is_cuda and y.is_cuda and x.dtype == torch.float32
+            and y.dtype == torch.float32 and x.device == y.device and x.shape == y.shape and x.dim() >= 1 and x.numel() > 0):
+        return False
+    first = members[0]
+    if not all(type(m) is SpectralDistance and m.is_plain() and m.power == first.power and m.normalized == first.normalized
+               and m.norm == first.norm and m.window.device == x.device and m.window.dtype == torch.float32 for m in members):
+        return False
+    if first.power not in (1, 2) or sorted(first.norm) not in (["L1"], ["L2"], ["L1", "L2"]):
+        return False
+    from . import ops
+    t = x.shape[-1]
+    return ops.spec_dist_on() and ops.spec_dist_supported([m.n_fft for m in members], t, x.numel() // t, first.power)
+
+
 class EncodecAudioDistance(nn.Module):
-    """rave/core.py:415-431."""
+    """rave/core.py:415-431.  Plain ``SpectralDistance`` members that agree in ``power``, ``normalized`` and ``norm`` run all of
+    their scales as ONE autograd node on the HIP kernels where every scale is built (``_spec_dist_kernel``); any other list
+    runs member by member."""
 
     def __init__(self, scales, spectral_distance) -> None:
         super().__init__()
@@ -244,6 +278,14 @@ class EncodecAudioDistance(nn.Module):
 
     def forward(self, x, y):
         waveform_distance = self.waveform_distance(x, y)
+        members = list(self.spectral_distances)
+        if members and _spec_dist_kernel(x, y, members):
+            from . import ops
+            first = members[0]
+            spectral_distance = ops.multiscale_spec_distance(x.reshape(-1, x.shape[-1]), y.reshape(-1, y.shape[-1]),
+                                                             [m.window for m in members], [m.n_fft for m in members],
+                                                             first.norm, first.power, first.normalized)
+            return {"waveform_distance": waveform_distance, "spectral_distance": spectral_distance}
         spectral_distance = 0
         for dist in self.spectral_distances:
             spectral_distance = spectral_distance + dist(x, y)

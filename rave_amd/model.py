@@ -862,7 +862,7 @@ def build_v2(n_channels: int = 1, capacity: int = 96, ratios=(4, 4, 4, 2), laten
              spectral_capacity: int = 32, gru_layers: int = 0, mel_input: bool = False, n_fft: int = 2048,
              hop_length: int = 256, n_mels: int = 128, encoder_ratios=(2, 2, 2), encoder_dilations=(1,),
              latent_analysis: bool = False, hip_frontend: bool = False, phase_distance: bool = False,
-             gan_loss: str = "hinge") -> RAVE:
+             gan_loss: str = "hinge", encodec_distance: bool = False) -> RAVE:
     """configs/v1.gin + configs/v2.gin transcribed (cf. oracle/ref_models.py for the citations).
     ``snake`` / ``adain`` add the generator-side overlays of configs/v3.gin (snake.gin: every activation
     -> blocks.Snake; adain.gin: AdaptiveInstanceNormalization before every unit); ``causal`` =
@@ -881,7 +881,12 @@ def build_v2(n_channels: int = 1, capacity: int = 96, ratios=(4, 4, 4, 2), laten
     normalised complex multi-scale STFT) as rave_amd/configs/mi355x_phase.gin does: the step then logs and trains on
     ``fullband_phase_distance`` as well; off by default.
     ``gan_loss``: "hinge" (every stock config), "ls" or "nonsaturating" -- losses.hinge_gan / ls_gan / nonsaturating_gan
-    (rave/core.py:151-170; the gin route: rave_amd/configs/mi355x_gan_loss.gin)."""
+    (rave/core.py:151-170; the gin route: rave_amd/configs/mi355x_gan_loss.gin).
+    ``encodec_distance`` binds the fullband distance to losses.EncodecAudioDistance over the plain losses.SpectralDistance
+    (scales 2048 ... 128, L1 + L2, power 1, normalised) as rave_amd/configs/mi355x_encodec.gin does: the step then logs and trains
+    on ``fullband_waveform_distance`` as well; off by default."""
+    if phase_distance and encodec_distance:
+        raise ValueError("build_v2: phase_distance and encodec_distance both bind the fullband distance; choose one")
     if gan_loss not in losses.GAN_LOSSES:
         raise ValueError(f"build_v2: gan_loss {gan_loss!r}, expected one of {sorted(losses.GAN_LOSSES)}")
     ratios = list(ratios)
@@ -958,6 +963,10 @@ def build_v2(n_channels: int = 1, capacity: int = 96, ratios=(4, 4, 4, 2), laten
         full_dist = partial(losses.WeightedInstantaneousSpectralDistance, weighted=True,
                             multiscale_stft=partial(losses.MultiScaleSTFT, scales=[2048, 1024, 512, 256, 128],
                                                     sample_rate=sampling_rate, magnitude=False, normalized=True))
+    if encodec_distance:    # rave_amd/configs/mi355x_encodec.gin: the fullband distance only, the multiband one stays
+        full_dist = partial(losses.EncodecAudioDistance, scales=[2048, 1024, 512, 256, 128],
+                            spectral_distance=partial(losses.SpectralDistance, sampling_rate=sampling_rate, norm=["L1", "L2"],
+                                                      power=1, normalized=True))
     model = RAVE(latent_size=latent_size, sampling_rate=sampling_rate,
                  pqmf=partial(pqmf.CachedPQMF, attenuation=100, n_band=n_band),
                  encoder=enc, decoder=dec, discriminator=disc, phase_1_duration=1000000,

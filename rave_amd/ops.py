@@ -1479,6 +1479,138 @@ def multiscale_inst_freq_distance(x: Tensor, y: Tensor, windows, scales, weighte
     return (sd, pd, if_outs) if debug_if else (sd, pd)
 
 
+# --------------------------------------------------------------------------- plain SpectralDistance (Encodec-style loss)
+def spec_dist_supported(scales, t: int, rows: int, power) -> bool:
+    if power not in (1, 2) or not 1 <= len(scales) <= 8:
+        return False
+    return all(L.lib.rh_spec_dist_supported(int(n), int(n) // 4, int(t), int(rows), int(power)) == 1 for n in scales)
+
+
+def spec_dist_on() -> bool:
+    """``RH_SPEC_DIST=0``: the torch composition on every device (diagnostics, tools/bench_spectral_distance.py's other leg)."""
+    return os.environ.get("RH_SPEC_DIST", "1") != "0"
+
+
+def spec_dist_spectrum(x: Tensor, window: Tensor, n_fft: int, power, normalized: bool) -> Tensor:
+    """(..., T) -> (..., n_fft / 2 + 1, frames), torch.stft(center=False) layout: torchaudio Spectrogram(n_fft, hop = n_fft / 4,
+    power, normalized, center=False) as a torch composition (``SpectralDistance.spec`` without ``mel``)."""
+    w = window.to(x.dtype)
+    fr = x.unfold(-1, n_fft, n_fft // 4) * w                            # (..., frames, n_fft): no padding (center=False)
+    s = torch.fft.rfft(fr, dim=-1).transpose(-1, -2)
+    if normalized:
+        s = s / w.pow(2.0).sum().sqrt()
+    if power is None:
+        return s
+    return s.abs() if power == 1.0 else s.abs().pow(power)
+
+
+def spec_dist_compose(x: Tensor, y: Tensor, window: Tensor, n_fft: int, norms, power, normalized: bool):
+    """SpectralDistance.forward without ``mel`` as the reference states it (rave/core.py:446-490) on whatever device and dtype
+    the signals have: what CPU tensors, other dtypes, ``power=None`` and unbuilt sizes take, and what
+    tools/bench_spectral_distance.py times against the kernels."""
+    from .losses import mean_difference
+    x = spec_dist_spectrum(x, window, n_fft, power, normalized)
+    y = spec_dist_spectrum(y, window, n_fft, power, normalized)
+    distance = 0
+    for norm in norms:
+        distance = distance + mean_difference(y, x, norm)
+    return distance
+
+
+_SPEC_SCALE = {}
+
+
+def _spec_dist_scale(window: Tensor) -> float:
+    """spectrogram_scale(window), cached per tensor OBJECT and version (an address is reused once a tensor is freed, so the
+    entry holds a weak reference and counts only while it still points at this tensor): the host read happens outside any
+    capture."""
+    import weakref
+    k = id(window)
+    hit = _SPEC_SCALE.get(k)
+    if hit is not None and hit[0]() is window and hit[1] == window._version:
+        return hit[2]
+    for dead in [i for i, h in _SPEC_SCALE.items() if h[0]() is None]:
+        del _SPEC_SCALE[dead]
+    s = spectrogram_scale(window)
+    _SPEC_SCALE[k] = (weakref.ref(window), window._version, s)
+    return s
+
+
+class _MultiScaleSpecDistFn(torch.autograd.Function):
+    """The plain SpectralDistance over ALL scales of an EncodecAudioDistance as one autograd node (rave/core.py:415-490): per
+    scale one rh_spec_dist_fwd_f32 launch, one ordered finalize for all of them; backward: per scale one rh_spec_dist_bwd_f32
+    launch accumulating into one dx / dy buffer, for the sides that need a gradient.  Nothing but the two waveforms is saved."""
+
+    @staticmethod
+    def forward(ctx, x, y, scales, use_l1: bool, use_l2: bool, power: int, scale_of, *windows):
+        x = _chk(x, "x"); y = _chk(y, "y")
+        if x.shape != y.shape or x.dim() != 2:
+            raise RuntimeError("rave_amd multiscale_spec_distance: expects two (rows, T) tensors of equal shape")
+        rows, t = x.shape
+        if not spec_dist_supported(scales, t, rows, power):
+            raise RuntimeError(f"rave_amd multiscale_spec_distance: scales {tuple(scales)} at T = {t}, rows = {rows}, power = {power} "
+                               "are not built (rh_spec_dist_supported)")
+        s = L.stream()
+        dev = x.device
+        ns = len(scales)
+        parts, inv_n = [], []
+        for n_fft, win, sc in zip(scales, windows, scale_of):
+            win = _chk(win, "window")
+            nbytes = L.lib.rh_spec_dist_workspace_bytes(n_fft, t, rows)
+            ws = torch.empty(max(nbytes // 4, 1), device=dev, dtype=torch.float32)
+            L.check(L.lib.rh_spec_dist_fwd_f32(L.ptr(x), L.ptr(y), L.ptr(win), L.ptr(_twiddle(n_fft, dev)), rows, t, n_fft, power, sc,
+                                               L.ptr(ws), nbytes, s), "spec_dist_fwd")
+            parts.append((ws, nbytes))
+            inv_n.append(1.0 / (rows * ((t - n_fft) // (n_fft // 4) + 1) * (n_fft // 2 + 1)))
+        key = (tuple(inv_n), str(dev))
+        if key not in _INV_N and not torch.cuda.is_current_stream_capturing():
+            _INV_N[key] = torch.tensor(inv_n, dtype=torch.float32, device=dev)
+        inv = _inv_n_cached(tuple(inv_n), dev)
+        sums = torch.empty(ns, 2, device=dev, dtype=torch.float32)
+        out = torch.empty((), device=dev, dtype=torch.float32)
+        pp = (C.c_void_p * ns)(*[w.data_ptr() for w, _ in parts])
+        nb = (C.c_int64 * ns)(*[b for _, b in parts])
+        L.check(L.lib.rh_spec_dist_finalize_all_f32(pp, nb, ns, L.ptr(inv), int(use_l1), int(use_l2), L.ptr(sums), L.ptr(out), s),
+                "spec_dist_finalize_all")
+        ctx.save_for_backward(*windows, x, y)
+        ctx.meta = (rows, t, tuple(scales), bool(use_l1), bool(use_l2), power, tuple(scale_of))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        rows, t, scales, use_l1, use_l2, power, scale_of = ctx.meta
+        ns = len(scales)
+        windows = ctx.saved_tensors[:ns]
+        x, y = ctx.saved_tensors[ns:]
+        dev = x.device
+        g = g.contiguous().reshape(1).float()
+        s = L.stream()
+        need = (ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        outs = [torch.empty(rows, t, device=dev, dtype=torch.float32) if nd else None for nd in need]
+        if any(need):
+            for i, n_fft in enumerate(scales):
+                L.check(L.lib.rh_spec_dist_bwd_f32(L.ptr(x), L.ptr(y), L.ptr(windows[i]), L.ptr(_twiddle(n_fft, dev)), rows, t, n_fft,
+                                                   power, scale_of[i], int(use_l1), int(use_l2), L.ptr(g),
+                                                   None if outs[0] is None else L.ptr(outs[0]),
+                                                   None if outs[1] is None else L.ptr(outs[1]), 1 if i > 0 else 0, s), "spec_dist_bwd")
+        return (outs[0], outs[1], None, None, None, None, None) + (None,) * ns
+
+
+def multiscale_spec_distance(x: Tensor, y: Tensor, windows, scales, norms, power, normalized: bool) -> Tensor:
+    """sum over the scales of sum over the norms of mean_difference(|Sy|^power, |Sx|^power, norm) (rave/core.py:415-490, the plain
+    SpectralDistance) for (rows, T) f32 signals on the GPU, differentiable in both: ONE autograd node
+    (rave_amd/csrc/spec_dist.hip).  ``windows``: one plain (n_fft,) window per scale; ``normalized`` divides every spectrum by
+    sqrt(sum(window^2)); ``norms``: "L1", "L2" or both, each at most once; ``power`` 1 or 2."""
+    scales = tuple(int(s) for s in scales)
+    norms = (norms,) if isinstance(norms, str) else tuple(norms)
+    if not norms or sorted(norms) not in (["L1"], ["L2"], ["L1", "L2"]):
+        raise RuntimeError(f"rave_amd multiscale_spec_distance: norms {norms!r}, expected 'L1', 'L2' or both, each once")
+    if x.data_ptr() == y.data_ptr():        # the kernels read two buffers
+        y = y.clone()
+    scale_of = tuple(_spec_dist_scale(w) if normalized else 1.0 for w in windows)
+    return _MultiScaleSpecDistFn.apply(x, y, scales, "L1" in norms, "L2" in norms, int(power), scale_of, *windows)
+
+
 # --------------------------------------------------------------------------- mel-spectrogram encoder input
 def mel_supported(n_fft: int, hop: int, n_mels: int, t: int, rows: int) -> bool:
     return L.lib.rh_mel_supported(int(n_fft), int(hop), int(n_mels), int(t), int(rows)) == 1
